@@ -10,11 +10,23 @@ mask + FAST(20, NMS), the first (2000 - n) corners stereo-matched (11x11 LK,
 maxLevel 3, 30 it), |yR - yL| < 40, DLT triangulation, z > 0, world frame by the
 estimated pose (R:src/tracking.cpp:240-269; every frame a keyframe that tops the
 set up to 2000 features). Frames are synthetic KITTI-sized stereo renders
-(svo_amd/scene.py), uploaded to HBM before the timed region. Multi-GPU: one
+(svo_amd/scene.py), uploaded to HBM before the timed region; 16 distinct sequences
+are rendered per GPU and every batch slot advances its own copy of one of them
+(--distinct 0: one render per slot, which takes the host ~100 s). Multi-GPU: one
 process per GPU, each advancing its own batch of independent sequences (weak
 scaling, no collective on the data path).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--seq S] [--config kitti|1080p|4k]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the
+headline, its per-step statistics and the LK roofline, all taken from the timed
+window itself). --full adds every measurement that takes runs of its own: the side
+workloads (single stream, bucketed, forward, ORB, streamed ingest, OpenCV-order LK),
+the pyramid and FAST rooflines (timed alone) and the CPU baseline; each can still be
+switched off there with its --no-* option. --dump-outputs DIR writes what the last
+timed step left for a caller (poses, features, map points of every sequence) as
+DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -330,6 +342,110 @@ def slowest_step(step_s, diag, warmup):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+STEP_COUNTS = ("lk_iterations", "tracked", "inliers", "added", "features", "keyframes")
+
+
+def dump_outputs(path, fe, n_seq, n_features, last_stats):
+    """What the last timed step left for a caller of the front end, one .npy per
+    array (float64 unless noted), every sequence of this rank in batch order:
+      poses         (S, 6)       rotation vector, translation (Frontend.pose)
+      counts        (S,)         current features per sequence
+      features      (S, C, 2)    float32 pixel positions, rows >= counts[s] zero
+      map_points    (S, C, 3)    world positions of the features' map points, rows >= counts[s] zero
+      step_counts   (6,)         the step's integer statistics, in STEP_COUNTS order
+    C = n_features (or the largest count, if a sequence holds more). The inputs are
+    seeded renders, so two builds run with the same arguments are comparable array
+    for array. 256 sequences x 2000 features are 16 MB; a batch over 64 MB (4k at
+    --seq 256) is cut to its first S sequences that fit."""
+    os.makedirs(path, exist_ok=True)
+    poses = np.zeros((n_seq, 6))
+    feats, points = [], []
+    for s in range(n_seq):
+        r, t = fe.pose(s)
+        poses[s, :3], poses[s, 3:] = r, t
+        feats.append(fe.features(s))
+        points.append(fe.map_points(s))
+    counts = np.array([len(f) for f in feats], np.float64)
+    cap = max(n_features, int(counts.max()) if n_seq else 0)
+    features = np.zeros((n_seq, cap, 2), np.float32)
+    map_points = np.zeros((n_seq, cap, 3))
+    for s in range(n_seq):
+        features[s, :len(feats[s])] = feats[s]
+        map_points[s, :len(points[s])] = points[s]
+    # at most 64 MB in all: the first sequences that fit (a fixed sample of a larger batch)
+    per_seq = poses[0].nbytes + counts[0].nbytes + features[0].nbytes + map_points[0].nbytes
+    keep = max(1, min(n_seq, (DUMP_MAX_BYTES - 4096) // per_seq))  # (4096: the .npy headers and step_counts)
+    arrays = {"poses": poses[:keep], "counts": counts[:keep], "features": features[:keep],
+              "map_points": map_points[:keep],
+              "step_counts": np.array([last_stats[k] for k in STEP_COUNTS], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+class PinnedPairs(list):
+    """P rendered stereo pairs of one sequence, (left, right) views into page-locked
+    host memory (the source of upload_resident's H2D copies)."""
+
+    def __init__(self, S, sc, P):
+        self.buf = S.PinnedBuffer((P, 2, sc.h, sc.w))
+        for t in range(P):
+            self.buf.array[t, 0], self.buf.array[t, 1] = sc.frame(t), sc.right(t)
+        super().__init__((self.buf.array[t, 0], self.buf.array[t, 1]) for t in range(P))
+
+    def close(self):
+        self.clear()
+        self.buf.close()
+
+
+# Resident frames per sequence are capped: a front end holds n_frames pyramids of
+# every slot (~0.95 GB per frame of 256 KITTI-size sequences), so --steps must not
+# size it. The scenes repeat exactly every CYCLE = 32 frames (frame t = pair t mod
+# 32), so past RING_FRAMES step n runs on ring frame ring_index(n): 1 .. T - 1, then
+# 32 .. T - 1 again and again. Frame 31 holds what frame T - 1 holds, and the
+# library keys its per-step buffers by t mod 2 and the derivative pyramids by t mod
+# 3, so the wrap length T - 32 is a multiple of 96 = lcm(32, 2, 3): the step after
+# a wrap then reads exactly what the unbounded sequence would (same poses and
+# features, checked against an unwrapped run). The wrap costs that one step its
+# prefetched first half (the library queues step t + 1's LK ahead only when frame
+# t + 1 is in the ring): ~4 ms once per 96 steps.
+CYCLE = 32
+WRAP = 96
+RING_FRAMES = CYCLE + WRAP
+
+
+def ring_frames(n: int) -> int:
+    """n_frames of a front end that is to run steps up to n - 2."""
+    return min(n, RING_FRAMES)
+
+
+def ring_index(t: int, T: int) -> int:
+    """The ring frame (of T = ring_frames(..)) that step t runs on."""
+    return t if t < T else CYCLE + (t - CYCLE) % (T - CYCLE)
+
+
+def upload_resident(fe, seqs, n_slots, T):
+    """Frames 0 .. T - 1 of every slot made resident before init: slot s holds its
+    own copy of sequence seqs[s mod len(seqs)] (PinnedPairs), frame t = pair t mod P.
+    One svo_frontend_queue_frames call per frame (contiguous H2D copies + the
+    batched ingest kernel for all slots) instead of a set_frame per slot and
+    frame, whose pitched 2-D copy takes ~3 ms each (200 s for 256 slots x 190
+    frames). queue_frames needs n_frames >= 4; below that, set_frame."""
+    n, P = len(seqs), len(seqs[0])
+    if T < 4:
+        for s in range(n_slots):
+            for t in range(T):
+                fe.set_frame(s, t, *seqs[s % n][t % P])
+        return
+    for t in range(T):
+        fe.queue_frames(t, [seqs[s % n][t % P][0] for s in range(n_slots)],
+                        [seqs[s % n][t % P][1] for s in range(n_slots)])
+        if t >= 4:
+            fe.upload_wait(t - 4)
+    for t in range(max(T - 4, 0), T):
+        fe.upload_wait(t)
+
+
 def forward_workload(S, SceneForward, ctx, W, H, N, ML, Sq, K, Wm, threads):
     """The harder sequence (svo_amd.scene.SceneForward: forward translation with
     parallax + a textured occluder sliding against the static world, 5-20 % RANSAC
@@ -337,22 +453,22 @@ def forward_workload(S, SceneForward, ctx, W, H, N, ML, Sq, K, Wm, threads):
     sequences per launch, Wm warm-up + K timed steps. 16 distinct sequences are
     rendered (the general renderer's host cost) and each fills Sq / 16 batch slots."""
     n_dist = min(Sq, 16)
-    T = Wm + K + 2  # as the headline: the last timed step queues the next LK
+    T = ring_frames(Wm + K + 2)  # as the headline: the last timed step queues the next LK
     scs = [SceneForward(W, H, seed=1000 + i) for i in range(n_dist)]
     P = min(T, 2 * scs[0].period)
-    pairs = [[(sc.frame(t), sc.right(t)) for t in range(P)] for sc in scs]
+    pairs = [PinnedPairs(S, sc, P) for sc in scs]
     fef = S.Frontend(ctx, S.FrontendConfig(W, H, scs[0].K, n_seq=Sq, n_frames=T, n_features=N, max_level=ML,
                                            host_threads=threads, timing=0))
-    for s in range(Sq):
-        for t in range(T):
-            fef.set_frame(s, t, *pairs[s % n_dist][t % P])
+    upload_resident(fef, pairs, Sq, T)
+    for p in pairs:
+        p.close()
     fef.init(0)
     for t in range(1, Wm + 1):
-        fef.step(t)
+        fef.step(ring_index(t, T))
     tot = {"tracked": 0, "inliers": 0, "added": 0, "hypotheses": 0}
     t1 = time.perf_counter()
     for t in range(Wm + 1, Wm + K + 1):
-        st = fef.step(t).as_dict()
+        st = fef.step(ring_index(t, T)).as_dict()
         for k in tot:
             tot[k] += st[k]
     fef.synchronize()
@@ -438,23 +554,23 @@ def orb_workload(S, SceneForward, ctx, W, H, ML, Sq, K, Wm, threads):
     / occluder scene so that tracks are lost and keyframes recur; timed like the
     headline (Sq sequences per launch, Wm warm-up + K timed steps)."""
     n_dist = min(Sq, 16)
-    T = Wm + K + 2
+    T = ring_frames(Wm + K + 2)
     scs = [SceneForward(W, H, seed=2000 + i) for i in range(n_dist)]
     P = min(T, 2 * scs[0].period)
-    pairs = [[(sc.frame(t), sc.right(t)) for t in range(P)] for sc in scs]
+    pairs = [PinnedPairs(S, sc, P) for sc in scs]
     feo = S.Frontend(ctx, S.FrontendConfig(W, H, scs[0].K, n_seq=Sq, n_frames=T, n_features=2000, max_level=ML,
                                            host_threads=threads, timing=0, use_orb=1,
                                            keyframe_rule=S.KF_REFERENCE, features_to_track=70))
-    for s in range(Sq):
-        for t in range(T):
-            feo.set_frame(s, t, *pairs[s % n_dist][t % P])
+    upload_resident(feo, pairs, Sq, T)
+    for p in pairs:
+        p.close()
     feo.init(0)
     for t in range(1, Wm + 1):
-        feo.step(t)
+        feo.step(ring_index(t, T))
     tot = {"tracked": 0, "inliers": 0, "added": 0, "keyframes": 0}
     t1 = time.perf_counter()
     for t in range(Wm + 1, Wm + K + 1):
-        st = feo.step(t).as_dict()
+        st = feo.step(ring_index(t, T)).as_dict()
         for k in tot:
             tot[k] += st[k]
     feo.synchronize()
@@ -481,11 +597,20 @@ def main():
     # 88.3k-89.1k, 256: 94.6k-94.9k (profiles/r04/e_seqcurve.txt); a step takes ~2.7 ms
     # at 256 (each sequence still advances ~370 frames/s)
     ap.add_argument("--seq", type=int, default=256, help="independent sequences per GPU (batched launches)")
+    ap.add_argument("--distinct", type=int, default=16,
+                    help="distinct sequences rendered per GPU; slot s runs its own copy of sequence s mod this "
+                         "(0: one per slot, 100 s of host rendering at the default size)")
     ap.add_argument("--config", default="kitti", choices=sorted(CONFIGS))
     ap.add_argument("--threads", type=int, default=0, help="host RANSAC threads (0 = auto)")
     ap.add_argument("--timing", type=int, default=2, choices=(1, 2, 3),
                     help="phase events: 1 all phases, 2 only LK/pyramid/FAST (lighter host tail), "
                          "3 the LK launches only (the roofline's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the side workloads, the pyramid and FAST "
+                         "rooflines (timed alone) and the CPU baseline (each has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (poses, features, map points) "
+                         "as DIR/<name>.npy (rank r > 0 of a multi-GPU run: DIR/rank<r>/)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single", action="store_true")
@@ -535,7 +660,7 @@ def main():
     # first half (its LK) as every step does, so the timed window holds K steps'
     # worth of work -- the LK of step Wm + 1, queued by the last warm-up step, runs
     # at the window's start, and that of step Wm + K + 1 is waited for at its end
-    T = Wm + K + 2
+    T = ring_frames(Wm + K + 2)  # (capped: past it the steps wrap, ring_index)
     device = local
     if world > 1:
         # One rank per GPU; ranks beyond the visible devices (a multi-rank rehearsal on a
@@ -544,10 +669,16 @@ def main():
         n_dev = torch.cuda.device_count()
         if n_dev > 0:
             device = local % n_dev
+    t_setup = time.perf_counter()
     ctx = S.Context(device)
     seeds = sequence_seeds(rank, Sq)
     scene_cls = SceneForward if args.scene == "forward" else Scene
-    scenes = [scene_cls(W, H, seed=sd) for sd in seeds]
+    # rendering is host work (~0.2 CPU-s per KITTI-size stereo pair: 100 s for 256
+    # sequences on 16 cores), so by default the first 16 sequences of this rank are
+    # rendered and slot s holds its own copy of sequence s mod 16, as in the side
+    # workloads; --distinct 0 renders every slot's own sequence
+    n_dist = Sq if args.distinct <= 0 else min(Sq, args.distinct)
+    scenes = [scene_cls(W, H, seed=sd) for sd in seeds[:n_dist]]
     # the synthetic camera ping-pongs with period 2 * scene.period (32 frames), so
     # P rendered stereo pairs per sequence are reused cyclically (frame t = pair
     # t mod P; rendering is host work outside the timing, all T frames resident)
@@ -555,19 +686,22 @@ def main():
     cfg = S.FrontendConfig(W, H, scenes[0].K, n_seq=Sq, n_frames=T, n_features=N, max_level=ML,
                            host_threads=args.threads, timing=args.timing)
     fe = S.Frontend(ctx, cfg)
+    print(f"[bench] rank {rank}: context and front end of {Sq} x {T} frames created "
+          f"({time.perf_counter() - t_setup:.1f} s)", file=sys.stderr, flush=True)
     pairs0 = None
-    keep_pairs = not (args.no_bucketed and args.no_opencv_order) and world == 1
-    all_pairs = []
-    for s, sc in enumerate(scenes):
-        pairs = [(sc.frame(t), sc.right(t)) for t in range(P)]
-        for t in range(T):
-            fe.set_frame(s, t, *pairs[t % P])
-        if s == 0:
-            pairs0 = pairs
-        if keep_pairs:
-            all_pairs.append(pairs)
-        if s % 16 == 15:
-            print(f"[bench] rank {rank}: {s + 1}/{Sq} sequences rendered and uploaded", file=sys.stderr, flush=True)
+    keep_pairs = args.full and not (args.no_bucketed and args.no_opencv_order) and world == 1
+    t1 = time.perf_counter()
+    all_pairs = [PinnedPairs(S, sc, P) for sc in scenes]
+    t2 = time.perf_counter()
+    upload_resident(fe, all_pairs, Sq, T)
+    print(f"[bench] rank {rank}: {n_dist} sequences rendered ({t2 - t1:.1f} s) and uploaded to {Sq} slots "
+          f"({time.perf_counter() - t2:.1f} s)", file=sys.stderr, flush=True)
+    if args.full:
+        pairs0 = all_pairs[0]
+    if not keep_pairs:
+        for pairs in all_pairs[1 if args.full else 0:]:
+            pairs.close()
+        all_pairs = []
     side = {"single": None, "bucketed": None, "forward": None, "orb": None, "stream": None, "opencv_order": None}
 
     def side_legs(close_fe):
@@ -577,14 +711,13 @@ def main():
         single = None
         if not args.no_single and world == 1:
             fe1 = S.Frontend(ctx, S.FrontendConfig(W, H, scenes[0].K, n_seq=1, n_frames=T, n_features=N, max_level=ML))
-            for t in range(T):
-                fe1.set_frame(0, t, *pairs0[t % P])
+            upload_resident(fe1, [pairs0], 1, T)
             fe1.init(0)
             for t in range(1, Wm + 1):
-                fe1.step(t)
+                fe1.step(ring_index(t, T))
             t1 = time.perf_counter()
             for t in range(Wm + 1, Wm + K + 1):
-                fe1.step(t)
+                fe1.step(ring_index(t, T))
             fe1.synchronize()
             single = K / (time.perf_counter() - t1)
             fe1.close()
@@ -599,7 +732,7 @@ def main():
         stream = None
         if not args.no_stream and args.scene == "rot" and world == 1:
             print("[bench] streamed-ingest workloads (grey, BGR)", file=sys.stderr, flush=True)
-            firsts = all_pairs[:16] if all_pairs else None
+            firsts = all_pairs[:16] if len(all_pairs) >= min(Sq, 16) else None
             stream = {kind: stream_workload(S, Scene, ctx, W, H, N, ML, Sq, K, Wm, args.threads, kind == "bgr",
                                             scenes[0].K, firsts) for kind in ("grey", "bgr")}
         # (last when the legs run first: the headline's own workload, so the GPU
@@ -612,15 +745,13 @@ def main():
             """The headline batch (same frames) under another configuration: frames/s, ms/step."""
             fev = S.Frontend(ctx, S.FrontendConfig(W, H, scenes[0].K, n_seq=Sq, n_frames=T, n_features=N, max_level=ML,
                                                    host_threads=args.threads, timing=0, **kw))
-            for s, pairs in enumerate(all_pairs):
-                for t in range(T):
-                    fev.set_frame(s, t, *pairs[t % P])
+            upload_resident(fev, all_pairs, Sq, T)
             fev.init(0)
             for t in range(1, Wm + 1):
-                fev.step(t)
+                fev.step(ring_index(t, T))
             t1 = time.perf_counter()
             for t in range(Wm + 1, Wm + K + 1):
-                fev.step(t)
+                fev.step(ring_index(t, T))
             fev.synchronize()
             dtv = time.perf_counter() - t1
             fev.close()
@@ -643,7 +774,7 @@ def main():
                     opencv_order=opencv_order)
 
     legs_after = args.legs == "after" or world > 1
-    if not legs_after:
+    if args.full and not legs_after:
         side_legs(close_fe=lambda: None)
     fe.init(0)
     try:
@@ -658,7 +789,7 @@ def main():
             # not sit between the warm-up and the timed window (the window would
             # start on an idle GPU with LK(Wm + 1) already done)
             fe.reset_times()
-        st = fe.step(t).as_dict()
+        st = fe.step(ring_index(t, T)).as_dict()
         feats_after[t] = st["features"]
     tot = {"lk_iterations": 0, "tracked": 0, "inliers": 0, "added": 0, "hypotheses": 0,
            "host_ms_hyp": 0.0, "host_ms_fit": 0.0, "host_ms_wait": 0.0, "host_ms_wait_post": 0.0,
@@ -670,7 +801,7 @@ def main():
     t0 = time.perf_counter()
     tp = t0
     for t in range(Wm + 1, Wm + K + 1):
-        st = fe.step(t).as_dict()
+        st = fe.step(ring_index(t, T)).as_dict()
         now = time.perf_counter()
         step_s.append(now - tp)
         tp = now
@@ -686,6 +817,9 @@ def main():
     fps = frames / dt_max
     lk_iters_total = allreduce_sum(dist, float(tot["lk_iterations"]))
     phases = fe.phase_times()
+    if args.dump_outputs and step_diag:
+        out_dir = args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}")
+        dump_outputs(out_dir, fe, Sq, N, step_diag[-1])
 
     if rank != 0:
         return
@@ -717,7 +851,7 @@ def main():
     # timed region; the in-step average is reported beside it)
     pyr_ms, pyr_n = phases.get("pyramid", (0.0, 0))
     pyr_instep_s = pyr_ms / max(pyr_n, 1) / 1e3
-    pyr_avg_s = fe.time_pyramid(Wm + K, 20) / 1e3
+    pyr_avg_s = fe.time_pyramid(ring_index(Wm + K, T), 20) / 1e3 if args.full else 0.0
     pyr_bytes = Sq * pyr_bytes_per_frame(W, H, ML)
     der_bytes = Sq * deriv_bytes_per_frame(W, H, ML)
     # the chain's HBM bytes. Fused (SVO_PYR_FUSED=1, the default; c = the coarsest
@@ -741,11 +875,11 @@ def main():
     # FAST detection (the pre-detection stage: FAST-9 + cornerScore + NMS, unmasked)
     # of the last frame of every sequence, timed alone the same way; algorithmic
     # bytes = one read of each W x H u8 frame (one raster pass)
-    fast_avg_s = fe.time_fast(Wm + K, 20) / 1e3 if hasattr(fe, "time_fast") else 0.0
+    fast_avg_s = fe.time_fast(ring_index(Wm + K, T), 20) / 1e3 if args.full and hasattr(fe, "time_fast") else 0.0
     fast_bytes = Sq * W * H
     fast_traffic = pmc_traffic(args.config, "fast_detect_q_kernel", Sq)  # one instance per config
     print("[bench] timed window done", file=sys.stderr, flush=True)
-    if legs_after:
+    if args.full and legs_after:
         side_legs(close_fe=fe.close)
     single, bucketed, forward, orb, stream, opencv_order = (
         side[k] for k in ("single", "bucketed", "forward", "orb", "stream", "opencv_order"))
@@ -763,12 +897,14 @@ def main():
         "dtype": "u8/int32 fixed-point (LK sums exact int, solve f32), f64 PnP",
         "data": "synthetic (rendered KITTI-size frames, seeded; no dataset on the box)"
                 + ("; SceneForward (translation + moving occluder)" if args.scene == "forward" else ""),
-        "config": {"workload": label, "sequences_per_gpu": Sq, "global_batch": Sq * world,
+        "config": {"workload": label, "sequences_per_gpu": Sq, "distinct_sequences_per_gpu": n_dist,
+                   "global_batch": Sq * world,
                    "features": N, "win": 21, "max_level": ML, "parallelism": f"{world} x independent sequences",
                    "host_cpus_rank0": len(host_cpus)},
         "lk_iters_per_s": round(lk_iters_total / dt_max, 1),
         "achieved_GBps_algorithmic": round(frames * frame_bytes(W, H, N, ML) / dt_max / 1e9, 2),
-        "side_legs": "after" if legs_after else "first",
+        "full": args.full,
+        "side_legs": ("after" if legs_after else "first") if args.full else None,
         "single_stream_fps": round(single, 2) if single else None,
         "bucketed": bucketed,
         "workloads": {"forward": forward, "orb_reference": orb, "stream": stream, "opencv_order": opencv_order},
@@ -818,7 +954,7 @@ def main():
             "avg_launch_us": round(pyr_avg_s * 1e6, 3),
             "timing": "alone, 20 launches (HIP events on the launch stream)",
             "in_step_avg_launch_us": round(pyr_instep_s * 1e6, 3),
-        },
+        } if args.full else None,
         "roofline_fast": {
             "kernel": f"fast_detect_q_kernel<32> (FAST-9 + cornerScore + NMS, 64x32 tiles), {Sq} frames per launch",
             "bound": "hbm",
@@ -830,9 +966,9 @@ def main():
             "algorithmic_bytes_per_launch": fast_bytes,
             "avg_launch_us": round(fast_avg_s * 1e6, 3),
             "timing": "alone, 20 launches (HIP events on the launch stream; includes the row-count reset)",
-        },
+        } if args.full else None,
     }
-    if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
         print("[bench] CPU baseline (oracle loop)", file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
     print(json.dumps(out), flush=True)

@@ -19,7 +19,7 @@ for r in csv.DictReader(open(f)):
 P
 done
 for lib in libsvo_gpu_cvold.so libsvo_gpu.so; do
-    SVO_GPU_LIB=$L/$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-single --no-bucketed \
+    SVO_GPU_LIB=$L/$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-single --no-bucketed \
         --no-forward --no-orb --no-stream > $O/cv.log 2>&1 || { tail -20 $O/cv.log; exit 1; }
     python -c "
 import json; d=json.loads(open('$O/cv.log').read().strip().splitlines()[-1]); print('$lib', 'headline', d['value'], 'opencv_order', d['workloads']['opencv_order']['value'], d['workloads']['opencv_order']['ms_per_step'])"

@@ -4,7 +4,7 @@
 #
 #   tests [PYTEST_ARGS]     pytest -m gpu (default: the whole suite)
 #   smoke                   __graft_entry__.smoke()
-#   bench [BENCH_ARGS]      one bench.py line (default: the driver's defaults)
+#   bench [BENCH_ARGS]      one bench.py line (default: the plain headline run; --full for every leg)
 #   fe                      frontend + new-parity tests, short bench
 #   trace [STEPS]           one steady step's GPU timeline + host trace
 #   prof TAG [BENCH_ARGS]   rocprofv3 --kernel-trace --stats of a bench run
@@ -25,7 +25,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out
 mkdir -p $O
-BQ="python bench.py --steps ${AB_STEPS:-20} --warmup 5 --no-cpu-baseline --no-single --no-bucketed --no-opencv-order --no-forward --no-orb --no-stream ${AB_ARGS:-}"
+BQ="python bench.py --full --steps ${AB_STEPS:-20} --warmup 5 --no-cpu-baseline --no-single --no-bucketed --no-opencv-order --no-forward --no-orb --no-stream ${AB_ARGS:-}"
 
 fail() { echo "FAILED: $1"; [ -n "$2" ] && tail -30 "$2"; exit 1; }
 
@@ -51,7 +51,7 @@ run_fe() {
     timeout -k 10 600 python -u -m pytest tests/test_frontend_gpu.py tests/test_ingest.py -x -v --timeout 300 \
         --timeout-method thread -p no:cacheprovider -m gpu > $O/fe_tests.log 2>&1 || fail fe-tests $O/fe_tests.log
     tail -1 $O/fe_tests.log
-    run_bench quick --steps 20 --warmup 5 --no-cpu-baseline
+    run_bench quick --full --steps 20 --warmup 5 --no-cpu-baseline
 }
 
 run_trace() {
@@ -231,7 +231,7 @@ run_round1() {
     local tag=$1
     run_tests
     run_smoke
-    run_bench "${tag}_driver" --gpus 1 --steps 20 --warmup 5
+    run_bench "${tag}_driver" --gpus 1 --steps 20 --warmup 5 --full
     run_prof "$tag" --gpus 1 --steps 20 --warmup 5
 }
 run_round2() {
@@ -240,8 +240,8 @@ run_round2() {
     run_pmc "$tag" 1080p 64
     run_pmc "$tag" 4k 32
     run_mix "$tag"
-    run_bench "${tag}_1080p" --config 1080p --seq 64 --steps 20 --warmup 5 --no-cpu-baseline
-    run_bench "${tag}_4k" --config 4k --seq 32 --steps 20 --warmup 5 --no-cpu-baseline
+    run_bench "${tag}_1080p" --full --config 1080p --seq 64 --steps 20 --warmup 5 --no-cpu-baseline
+    run_bench "${tag}_4k" --full --config 4k --seq 32 --steps 20 --warmup 5 --no-cpu-baseline
 }
 
 while [ $# -gt 0 ]; do

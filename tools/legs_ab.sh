@@ -12,7 +12,7 @@ for legs in ${LEGS:-first after}; do
         rm -rf $O/legs_$legs
         pre="rocprofv3 --kernel-trace -d $O/legs_$legs -o run --output-format csv --"
     fi
-    timeout -k 10 400 $pre python bench.py --steps 20 --warmup 5 --legs $legs --no-cpu-baseline --no-single \
+    timeout -k 10 400 $pre python bench.py --full --steps 20 --warmup 5 --legs $legs --no-cpu-baseline --no-single \
         --no-orb --no-stream --no-opencv-order > $O/legs_$legs.log 2>&1 || { echo "FAILED $legs"; tail -20 $O/legs_$legs.log; exit 1; }
     python3 -c "
 import json
