@@ -8,7 +8,7 @@ import pytest
 import oracle as O
 import svo_amd as S
 from oracle_loop import OracleLoop
-from svo_amd.scene import Scene, SceneForward
+from svo_amd.scene import STEREO_BF, Scene, SceneForward
 
 pytestmark = pytest.mark.gpu
 
@@ -510,3 +510,104 @@ def test_frontend_kernel_timers_leave_the_sequence_intact():
         if t in (2, 4):
             assert fe.time_fast(t + 1, 3) > 0
             assert fe.time_pyramid(t + 1, 2) > 0
+
+
+def far_rig(base, bf):
+    """`base` (Scene / SceneForward) with a stereo rig of fx * baseline `bf`: the right
+    images and the projection pair both follow it."""
+    class FarRig(base):
+        def right(self, t):
+            return super().right(t, bf)
+
+        def projections(self):
+            return super().projections(bf)
+    return FarRig
+
+
+def test_frontend_far_rig_keep_rule_at_subpixel_disparity():
+    """A rig of a hundredth of the scenes' baseline: the keyframes' stereo disparities
+    are -0.05 .. 0.23 px, so the DLT's sign of z decides the feature list (the keep
+    rule status && |yR - yL| < y_threshold && z > 0 of the keyframe append) -- the
+    oracle drops 4 of the 400 first candidates by z > 0 alone. Counts, bit-equal
+    feature lists, poses and map points step by step against the oracle loop."""
+    ctx = S.Context(0)
+    W, H, N, T = 320, 240, 400, 5
+    bf = STEREO_BF / 100
+    sc = far_rig(Scene, bf)(W, H, seed=3)
+    P_left, P_right = sc.projections()
+    assert P_right[0, 3] == np.float32(-bf)
+    # the oracle's side of the keyframe at init: what the disparities are and that z > 0 decides
+    L, R = sc.frame(0), sc.right(0)
+    cand = O.fast(L, 20, True)[:N, :2]
+    assert len(cand) == N
+    nr, st, _, _ = O.lk(L, R, cand, (11, 11), 3, (3, 30, 1e-3), 0, acc=O.ACC_EXACT, want_err=False)
+    keep = (st == 1) & (np.abs(nr[:, 1] - cand[:, 1]) < 40)
+    d = cand[keep, 0].astype(np.float64) - nr[keep, 0]
+    assert -0.1 < d.min() < 0 < d.max() < 0.5 and np.abs(d).min() >= 1e-3
+    behind = O.triangulate(P_left, P_right, cand[keep], nr[keep])[1][:, 2] <= 0
+    assert behind.sum() == 4 and keep.sum() == N
+    fe = make_frontend(ctx, [sc], T, N, P_left=P_left, P_right=P_right)
+    fe.init(0)
+    ref = OracleLoop(far_rig(Scene, bf)(W, H, seed=3), N).init(0)
+    assert len(ref.pts) == N - 4
+    assert np.array_equal(fe.features(0), ref.pts)
+    np.testing.assert_allclose(fe.map_points(0), ref.X, rtol=2e-5, atol=1e-6)
+    for t in range(1, T):
+        st = fe.step(t).as_dict()
+        rs = ref.step(t)
+        _compare_step(fe, ref, st, rs, t)
+    fe.close()
+
+
+def test_frontend_far_rig_ransac_inliers_at_small_disparity():
+    """SceneForward on a rig of a fortieth of the baseline: the map points come from
+    sub-pixel disparities, and the RANSAC drops 20-60 % of the tracked points per
+    step in the oracle -- the inlier counts, the feature lists, poses and map points
+    must still be the oracle's at every step."""
+    ctx = S.Context(0)
+    W, H, N, T = 320, 240, 400, 5
+    bf = STEREO_BF / 40
+    sc = far_rig(SceneForward, bf)(W, H, seed=3)
+    P_left, P_right = sc.projections()
+    fe = make_frontend(ctx, [sc], T, N, P_left=P_left, P_right=P_right)
+    fe.init(0)
+    ref = OracleLoop(far_rig(SceneForward, bf)(W, H, seed=3), N).init(0)
+    assert np.array_equal(fe.features(0), ref.pts)
+    drops = []
+    for t in range(1, T):
+        st = fe.step(t).as_dict()
+        rs = ref.step(t)
+        _compare_step(fe, ref, st, rs, t)
+        drops.append(1 - rs["inliers"] / rs["tracked"])
+    assert min(drops) > 0.2 and np.mean(drops) > 0.3, np.round(drops, 3)
+    fe.close()
+
+
+def test_frontend_bucket_global_tables_in_a_batch():
+    """bucket_size 8, per_bucket 4 at 640x376: 3888 buckets, 106 KiB of tables -- past
+    the LDS limit, so bucket_kernel<false> keeps them in each sequence's global
+    scratch behind its n bucket ids (scr + seq * scr_stride, then + n). Two sequences
+    in one batch, each against its own oracle loop with the same bucketing."""
+    ctx = S.Context(0)
+    W, H, N, T = 640, 376, 800, 4
+    seeds = (3, 8)
+    fe = make_frontend(ctx, [Scene(W, H, seed=s) for s in seeds], T, N, bucket_size=8, per_bucket=4)
+    fe.init(0)
+    refs = [OracleLoop(Scene(W, H, seed=s), N, bucket=(8, 4)).init(0) for s in seeds]
+    # the bucketing changes the candidates: the loops without it pick other features
+    plain = OracleLoop(Scene(W, H, seed=seeds[0]), N).init(0)
+    assert not np.array_equal(plain.pts, refs[0].pts)
+    for q, ref in enumerate(refs):
+        assert np.array_equal(fe.features(q), ref.pts), f"seq {q} features at init"
+    for t in range(1, T):
+        st = fe.step(t).as_dict()
+        rss = [r.step(t) for r in refs]
+        for k in ("tracked", "lk_iterations", "inliers", "added", "features"):
+            assert st[k] == sum(rs[k] for rs in rss), f"{k} differs at t={t}"
+        for q, ref in enumerate(refs):
+            assert np.array_equal(fe.features(q), ref.pts), f"seq {q} features differ at t={t}"
+            rv, tv = fe.pose(q)
+            np.testing.assert_allclose(rv, ref.pose[0], atol=1e-7)
+            np.testing.assert_allclose(tv, ref.pose[1], atol=1e-6)
+            np.testing.assert_allclose(fe.map_points(q), ref.X, rtol=2e-5, atol=1e-6)
+    fe.close()
