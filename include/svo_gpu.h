@@ -263,7 +263,14 @@ typedef struct svo_frontend svo_frontend;
 typedef struct svo_frontend_config {
     int width, height;      /* frame size */
     int n_seq;              /* sequences per batch */
-    int n_frames;           /* frames kept resident per sequence */
+    int n_frames;           /* frames kept resident per sequence. It also sizes the map:
+                               CAP * (n_frames + 2) points per sequence, CAP = n_features
+                               rounded up to 64. A resident run never fills it; a streamed
+                               ring (queue_frames, e.g. n_frames 4) does on a long run, and
+                               the keyframe that would overflow it first reclaims the slots
+                               of features no longer tracked (the live points move to the
+                               front, in order), so a run of any length follows the same
+                               loop. svo_frontend_map_points reads live features only. */
     int n_features;         /* features kept per frame (top-up target), e.g. 2000 */
     int max_level;          /* LK maxLevel, R:src/tracking.cpp:163 -> 3 */
     int win;                /* LK window, :163 -> 21 */

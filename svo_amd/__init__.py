@@ -57,7 +57,11 @@ def lib_path() -> str:
 
 # Live handles, closed at interpreter exit in dependency order (front ends and
 # images before the contexts they were made on): left to __del__, a context can
-# go first and its dependants then free into a destroyed context.
+# go first and its dependants then free into a destroyed context. The cyclic
+# collector does the same to objects it frees together (a failed test's traceback
+# holds its front end and its context; the weak sets below are cleared before
+# their __del__ run), so a context also keeps the native handles of its live
+# dependants (Context._deps) and destroys those first when it goes first.
 _LIVE = {"frontend": weakref.WeakSet(), "image": weakref.WeakSet(), "context": weakref.WeakSet()}
 
 
@@ -249,6 +253,7 @@ class Image:
 
     def __init__(self, ctx: "Context", handle, w: int, h: int, max_levels: int):
         self.ctx, self.handle, self.w, self.h, self.max_levels = ctx, handle, w, h, max_levels
+        ctx._deps[handle.value] = "image"
         _LIVE["image"].add(self)
 
     def level(self, l: int) -> np.ndarray:
@@ -287,7 +292,8 @@ class Image:
 
     def close(self):
         if self.handle:
-            lib().svo_image_destroy(self.ctx.handle, self.handle)
+            if self.ctx._deps.pop(self.handle.value, None):  # (else the context went first and took it along)
+                lib().svo_image_destroy(self.ctx.handle, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -326,6 +332,7 @@ class Context:
         if rc != 0:
             raise SvoError(f"svo_ctx_create(device={device}) failed: {rc} (no usable HIP device?)")
         self.handle = h
+        self._deps = {}  # native handle -> "frontend" / "image" of the live dependants
         _LIVE["context"].add(self)
 
     def _check(self, rc):
@@ -335,7 +342,15 @@ class Context:
 
     def close(self):
         if getattr(self, "handle", None):
-            lib().svo_ctx_destroy(self.handle)
+            L = lib()
+            for kind in ("frontend", "image"):  # dependants still alive go first
+                for h in [h for h, k in self._deps.items() if k == kind]:
+                    if kind == "frontend":
+                        L.svo_frontend_destroy(_vp(h))
+                    else:
+                        L.svo_image_destroy(self.handle, _vp(h))
+                    del self._deps[h]
+            L.svo_ctx_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -635,6 +650,7 @@ class Frontend:
         h = _vp()
         ctx._check(lib().svo_frontend_create(ctx.handle, C.byref(cfg), C.byref(h)))
         self.handle = h
+        ctx._deps[h.value] = "frontend"
         self._queued = {}  # ring slot -> (t, lefts, rights) of queue_frames, until upload_wait(t)
         _LIVE["frontend"].add(self)
 
@@ -773,7 +789,8 @@ class Frontend:
 
     def close(self):
         if getattr(self, "handle", None):
-            lib().svo_frontend_destroy(self.handle)  # waits for the front end's streams
+            if self.ctx._deps.pop(self.handle.value, None):  # (else the context went first and took it along)
+                lib().svo_frontend_destroy(self.handle)  # waits for the front end's streams
             self.handle = None
             self._queued = {}
 

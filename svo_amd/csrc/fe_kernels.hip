@@ -297,12 +297,44 @@ __global__ __launch_bounds__(kPostBlock) void post_lk_kernel(PostLkBatch B) {
     }
 }
 
+// The map of one sequence reclaimed in place: the map points of its n features
+// moved to slots 0 .. n - 1 in feature order, mid[i] = i. The ids of a feature list
+// are strictly increasing (stable compactions keep the order, an append numbers
+// its points from map_n on, and this renumbering keeps both), so mid[i] >= i: a
+// point never moves up, and with every read of a chunk before its writes
+// (block_compact_fn's discipline) no point is overwritten before it has moved.
+// n is uniform over the block.
+template <int BS>
+__device__ __forceinline__ void map_reclaim(double* __restrict__ map, int* __restrict__ mid, int n) {
+    __syncthreads();  // mid was just written by the compaction
+    for (int c0 = 0; c0 < n; c0 += BS) {
+        const int i = c0 + threadIdx.x;
+        double x = 0., y = 0., z = 0.;
+        if (i < n) {
+            const double* X = map + 3 * (size_t)mid[i];
+            x = X[0];
+            y = X[1];
+            z = X[2];
+        }
+        __syncthreads();
+        if (i < n) {
+            map[3 * (size_t)i] = x;
+            map[3 * (size_t)i + 1] = y;
+            map[3 * (size_t)i + 2] = z;
+            mid[i] = i;
+        }
+        __syncthreads();
+    }
+}
+
 // Outlier compaction by the inlier bits + the keyframe's take (tail_kernel's
 // body, BS threads); copy_cand: also copy the candidates to st_xy (the stereo
-// LK's input; a speculative prep already wrote them otherwise).
+// LK's input; a speculative prep already wrote them otherwise). map_n_out: the
+// sequence's map count the append starts from (T.map_n[s], after a reclaim).
 template <int BS>
 __device__ __forceinline__ void tail_body(const TailBatch& T, int s, bool copy_cand, int* wsum, int* base_s,
-                                          int* n_kept, int* take_out, int* cnt, double (*spart)[kSuffStats]) {
+                                          int* n_kept, int* take_out, int* map_n_out, int* cnt,
+                                          double (*spart)[kSuffStats]) {
     const size_t o = (size_t)s * T.cap;
     const uint32_t* __restrict__ bits = T.bits + (size_t)s * T.words_cap;
     if (T.stats_out) {
@@ -315,8 +347,18 @@ __device__ __forceinline__ void tail_body(const TailBatch& T, int s, bool copy_c
         T.xy_out + 2 * o, T.mid_out + o, wsum, base_s, cnt);
     // new-feature candidates of the keyframe: the first `take` masked corners
     int take = min(max(T.n_target[s] - n, 0), min(T.cand_n[s], T.cand_cap));
-    take = min(take, T.cap - n);
-    take = max(min(take, T.map_cap - T.map_n[s]), 0);
+    take = max(min(take, T.cap - n), 0);
+    // the map is full (a ring of few frames on a long run; never with resident
+    // frames, whose map holds a full take per frame): reclaim the slots of the
+    // features that are gone. Every thread reads map_n before the reclaim's first
+    // barrier, thread 0 rewrites it behind its last one.
+    int mn = T.map_n[s];
+    if (mn + take > T.map_cap) {
+        map_reclaim<BS>(T.map + 3 * (size_t)s * T.map_cap, T.mid_out + o, n);
+        mn = n;
+        if (threadIdx.x == 0) T.map_n[s] = n;
+    }
+    take = max(min(take, T.map_cap - mn), 0);  // (map_cap >= 2 cap: no bound once reclaimed)
     if (copy_cand) {
         const float* c = T.cand + (size_t)T.cand_elem * ((size_t)s * T.cand_cap);
         for (int j = threadIdx.x; j < take; j += BS) {
@@ -331,6 +373,7 @@ __device__ __forceinline__ void tail_body(const TailBatch& T, int s, bool copy_c
     }
     *n_kept = n;
     *take_out = take;
+    *map_n_out = mn;
 }
 
 __global__ __launch_bounds__(kFeBlock) void tail_kernel(TailBatch T) {
@@ -338,8 +381,8 @@ __global__ __launch_bounds__(kFeBlock) void tail_kernel(TailBatch T) {
     __shared__ int base_s;
     __shared__ int cnt[kCompactChunks * kFeBlock / 64];
     __shared__ double spart[kSuffThreads / 64][kSuffStats];
-    int n, take;
-    tail_body<kFeBlock>(T, blockIdx.x, true, wsum, &base_s, &n, &take, cnt, spart);
+    int n, take, mn;
+    tail_body<kFeBlock>(T, blockIdx.x, true, wsum, &base_s, &n, &take, &mn, cnt, spart);
 }
 
 // findLeftFeaturesInRight's filter + triangulateNewMapPoints for one stereo match:
@@ -358,13 +401,14 @@ __device__ __forceinline__ bool stereo_point(const float (&P)[24], float y_thres
 }
 
 // The append of the stereo matches of st_xy[0, take) of sequence s, n0 features
-// already kept: the filter and the points come from stereo_tri_kernel (A.st_X).
+// already kept and m0 map points held: the filter and the points come from
+// stereo_tri_kernel (A.st_X).
 template <int BS>
-__device__ __forceinline__ void append_body(const AppendBatch& A, int s, int n0, int take, int* wsum, int* base_sp) {
+__device__ __forceinline__ void append_body(const AppendBatch& A, int s, int n0, int take, int m0, int* wsum,
+                                            int* base_sp) {
     int& base_s = *base_sp;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const size_t o = (size_t)s * A.cap;
-    const int m0 = A.map_n[s];
     __syncthreads();  // base_s / wsum reuse after the caller's own block work
     if (tid == 0) base_s = 0;
     __syncthreads();
@@ -424,7 +468,7 @@ __global__ __launch_bounds__(BS) void append_kernel(AppendBatch A) {
     __shared__ int wsum[BS / 64];
     __shared__ int base_s;
     const int s = blockIdx.x;
-    append_body<BS>(A, s, A.n[s], A.st_n[s], wsum, &base_s);
+    append_body<BS>(A, s, A.n[s], A.st_n[s], A.map_n[s], wsum, &base_s);
 }
 
 template <int BS>
@@ -434,9 +478,9 @@ __global__ __launch_bounds__(BS) void keyframe_fused_kernel(TailBatch T, AppendB
     __shared__ int cnt[kCompactChunks * BS / 64];
     __shared__ double spart[kSuffThreads / 64][kSuffStats];
     const int s = blockIdx.x;
-    int n, take;
-    tail_body<BS>(T, s, false, wsum, &base_s, &n, &take, cnt, spart);
-    append_body<BS>(A, s, n, take, wsum, &base_s);
+    int n, take, mn;
+    tail_body<BS>(T, s, false, wsum, &base_s, &n, &take, &mn, cnt, spart);
+    append_body<BS>(A, s, n, take, mn, wsum, &base_s);
 }
 
 // one 64-lane wave per block: the candidates of a sequence are ~ the margin (tens),
@@ -465,7 +509,7 @@ __global__ __launch_bounds__(64, 6) void stereo_tri_kernel(StereoTriBatch B) {
 __global__ __launch_bounds__(kFeBlock) void stereo_prep_kernel(StereoPrepBatch B) {
     const int s = blockIdx.x;
     int spec = min(max(B.n_target[s] - B.n_tracked[s] + B.margin, 0), min(B.cand_n[s], B.cand_cap));
-    spec = max(min(min(spec, B.cap), B.map_cap - B.map_n[s]), 0);
+    spec = max(min(spec, B.cap), 0);
     const float* c = B.cand + (size_t)B.cand_elem * ((size_t)s * B.cand_cap);
     float* dst = B.st_xy + 2 * (size_t)s * B.cap;
     for (int j = threadIdx.x; j < spec; j += kFeBlock) {

@@ -643,6 +643,7 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
     tb.cand_elem = bucketed ? 2 : 3;
     tb.cand_cap = bucketed ? fe->BCAP : fe->KCAP;
     tb.cand_n = bucketed ? fe->bn : fe->kn;
+    tb.map = fe->map;
     tb.map_n = fe->map_n;
     tb.map_cap = fe->MAPCAP;
     tb.st_xy = fe->st_xy;
@@ -722,8 +723,6 @@ int fe_queue_spec(svo_frontend* fe, int t, bool early) {
     pb.cand_elem = bucketed ? 2 : 3;
     pb.cand_cap = bucketed ? fe->BCAP : fe->KCAP;
     pb.cand_n = bucketed ? fe->bn : fe->kn;
-    pb.map_n = fe->map_n;
-    pb.map_cap = fe->MAPCAP;
     pb.cap = fe->CAP;
     pb.n_target = fe->h_target;
     pb.margin = margin;
@@ -1887,7 +1886,7 @@ int svo_frontend_step(svo_frontend* fe, int t, svo_frontend_stats* stats) {
             // features untouched instead of aborting the batch
             for (int k = 0; k < r.n; k++) b[k >> 5] |= 1u << (k & 31);
         }
-        inl += r.ok ? (int64_t)r.maxGood : r.n;
+        inl += kept;  // (no model from 4 or more points: every point is an outlier)
         fe->pred_iters[s] = (r.ok && r.n > 0)
                                 ? std::max(1, RansacSeq::predict_iters(c.pnp_confidence,
                                                                        (double)(r.n - r.maxGood) / r.n,

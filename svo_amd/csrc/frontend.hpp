@@ -51,9 +51,16 @@ hipError_t launch_finalize_map(const PendingMap& pm, int nseq, hipStream_t st);
 // The step's tail, part 1, one block per sequence: stable compaction by the
 // RANSAC inlier bits (read from host-coherent memory; R:src/tracking.cpp:218-229)
 // into xy_out / mid_out / n_out, then the keyframe's new-feature candidates: the
-// first take = min(n_target[s] - n, candidates, capacity) masked FAST corners
+// first take = min(n_target[s] - n, cand_n, cand_cap, cap - n) masked FAST corners
 // (extractFeatures, :74-92), copied to st_xy (the stereo LK's input) with their
-// count in st_n.
+// count in st_n. The map has map_cap slots per sequence and map_n only grows with
+// the appends, so in this order: (1) the compaction; (2) if map_n + take >
+// map_cap the kernel reclaims the map -- only the kept features' map points are
+// ever read again, so they move to slots 0 .. n - 1 in feature order (mid_out[i]
+// = i, map_n = n); nothing is pending then (the step's post-LK finalized the last
+// keyframe's points); (3) take = min(take, map_cap - map_n), a bounds guard only
+// (map_cap >= 4 cap, n <= cap: it never binds after a reclaim); (4) the append
+// numbers its points from map_n on.
 struct TailBatch {
     const int* n_in;
     const uint32_t* bits;  // [s][words_cap], host-coherent
@@ -68,7 +75,8 @@ struct TailBatch {
     const float* cand;  // candidates, cand_elem floats each, cand_cap per sequence
     int cand_elem, cand_cap;
     const int* cand_n;
-    const int* map_n;
+    double* map;  // [s][map_cap]
+    int* map_n;
     int map_cap;
     float* st_xy;  // [s][cap]
     int* st_n;     // [s]
@@ -115,8 +123,9 @@ hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st);
 // tracked count n_tracked (post-LK) and the FAST candidates are known, i.e. before
 // the RANSAC: the keyframe takes the first take = min(n_target - kept, ...)
 // candidates, kept <= n_tracked inliers, so the first
-//   spec = min(n_target[s] - n_tracked + margin, cand_n, cand_cap, cap, map_cap - map_n)
-// candidates cover take whenever RANSAC drops at most `margin` points. They are
+//   spec = min(n_target[s] - n_tracked + margin, cand_n, cand_cap, cap)
+// candidates cover take whenever RANSAC drops at most `margin` points (the map's
+// capacity does not bound them: the keyframe reclaims the map, TailBatch). They are
 // copied to st_xy with their count in spec_n, and their stereo LK runs beside
 // the host's RANSAC (a feature's LK depends on nothing but its own point).
 struct StereoPrepBatch {
@@ -124,8 +133,7 @@ struct StereoPrepBatch {
     const float* cand;
     int cand_elem, cand_cap;
     const int* cand_n;
-    const int* map_n;
-    int map_cap, cap, margin;
+    int cap, margin;
     const int* n_target;  // [s], as TailBatch::n_target
     float* st_xy;
     int* spec_n;

@@ -96,6 +96,9 @@ class OracleLoop:
         self.pose_T = (np.eye(3), np.zeros(3))
         self.pts, self.X = self._keyframe(self.img, right, cand, *self.pose_T)
         self.pose = (np.zeros(3), np.zeros(3))
+        # creation numbers of the features' map points (the front end's map ids until it reclaims its map)
+        self.mid = np.arange(len(self.pts))
+        self.n_created = len(self.pts)
         self.kf_prev = True  # frame t0 is a keyframe (lastFrameID == 0)
         return self
 
@@ -105,7 +108,7 @@ class OracleLoop:
         nx, st, _, it = O.lk(self.img, B, self.pts, TEMPORAL["win"], self.max_level, TEMPORAL["criteria"],
                              TEMPORAL["flags"], acc=self.acc, want_err=False)
         keep = st == 1
-        p2, X2 = nx[keep], self.X[keep]
+        p2, X2, m2 = nx[keep], self.X[keep], self.mid[keep]
         stats = {"lk_iterations": int(it.sum()), "tracked": int(keep.sum())}
         rv, tv = np.zeros(3), np.zeros(3)
         self.last_pnp = (X2, p2, 0)  # the RANSAC's inputs (tests replay its hypotheses)
@@ -113,10 +116,10 @@ class OracleLoop:
             rc, rv_, tv_, inl, nh = O.solve_pnp_ransac(X2, p2, self.sc.K)
             self.last_pnp = (X2, p2, nh)
             if rc == 1:
-                p2, X2 = p2[inl], X2[inl]
+                p2, X2, m2 = p2[inl], X2[inl], m2[inl]
                 rv, tv = rv_, tv_
             else:  # no model: every feature is an outlier (R:src/tracking.cpp:218-229)
-                p2, X2 = p2[:0], X2[:0]
+                p2, X2, m2 = p2[:0], X2[:0], m2[:0]
             stats["hypotheses"] = nh
         self.pose = (rv, tv)
         self.pose_T = pose_inverse(rv, tv)
@@ -131,6 +134,9 @@ class OracleLoop:
         newL, newX = self._keyframe(B, Br, cand[:need], *self.pose_T)
         self.pts = np.concatenate([p2, newL]).astype(np.float32)
         self.X = np.concatenate([X2, newX]) if len(newL) else X2
+        self.mid = np.concatenate([m2, self.n_created + np.arange(len(newL))])
+        self.n_created += len(newL)
+        stats["take"] = len(cand[:need])  # candidates handed to the stereo LK
         stats["added"] = len(newL)
         stats["features"] = len(self.pts)
         self.img = B

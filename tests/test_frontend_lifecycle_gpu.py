@@ -57,3 +57,22 @@ def test_front_ends_share_the_context_streams_and_results_hold():
     _same(ref, a)
     _same(ref, b)
     _same(ref, c)
+
+
+def test_context_closed_first_takes_its_dependants_along():
+    """A context closed while a front end and an image made on it are alive (the
+    order the cyclic collector may pick for objects it frees together) destroys
+    them first; their own close() afterwards is a no-op, and a new context works."""
+    ctx = S.Context(0)
+    _, _, fe = _run(ctx, 50, close=False)
+    img = ctx.image(Scene(W, H, seed=50).frame(0), 3)
+    assert len(ctx._deps) == 2
+    ctx.close()
+    assert ctx.handle is None and not ctx._deps
+    fe.close()
+    img.close()
+    fe.close()
+    assert fe.handle is None and img.handle is None
+    ref, _, _ = _run(S.Context(0), 50)
+    again, _, _ = _run(S.Context(0), 50)
+    _same(ref, again)

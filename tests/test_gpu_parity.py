@@ -510,6 +510,35 @@ def test_pnp_ransac_too_few_points(ctx):
         ctx.solve_pnp_ransac(np.zeros((3, 3)), np.zeros((3, 2), np.float32), np.eye(3))
 
 
+@pytest.mark.parametrize("n", [4, 5, 6, 7])
+def test_pnp_ransac_small_sets(ctx, n):
+    """solvePnPRansac on 4 and 5 points (solved directly, every point an inlier: seed
+    2 at n = 4 is a wild pose, |t| = 10) and on 6 and 7 (the smallest sets the
+    5-point subsets are drawn from): return code, inlier set and pose."""
+    for seed in range(3):
+        sc, X, uv, _ = _pnp_problem(n=n, seed=seed, outlier_frac=0.0)
+        ok, rv, tv, inl = ctx.solve_pnp_ransac(X, uv, sc.K)
+        rc, rv_o, tv_o, inl_o, _ = O.solve_pnp_ransac(X, uv, sc.K)
+        assert rc == 1 and ok, f"n={n} seed={seed}"
+        assert np.array_equal(inl, inl_o) and len(inl_o) == n
+        np.testing.assert_allclose(rv, rv_o, atol=1e-7)
+        np.testing.assert_allclose(tv, tv_o, atol=1e-6)
+
+
+def test_pnp_ransac_no_model(ctx):
+    """40 random correspondences: all 100 hypotheses tried, none with more than 4
+    inliers -> no model (return 0), no inliers, rvec / tvec left untouched."""
+    sc = Scene(1241, 376, seed=0)
+    rng = np.random.default_rng(100)
+    X = np.c_[rng.uniform(-15, 15, 40), rng.uniform(-4, 4, 40), rng.uniform(6, 40, 40)]
+    uv = np.c_[rng.uniform(0, 1241, 40), rng.uniform(0, 376, 40)].astype(np.float32)
+    rc, _, _, inl_o, nh = O.solve_pnp_ransac(X, uv, sc.K)
+    assert rc == 0 and nh == 100 and len(inl_o) == 0
+    ok, rv, tv, inl = ctx.solve_pnp_ransac(X, uv, sc.K)
+    assert not ok and len(inl) == 0
+    assert not rv.any() and not tv.any()
+
+
 def test_lk_negative_bilinear_weight_case(ctx, lk_kernel):
     """OpenCV's rounded weights can make iw11 = 2^14 - iw00 - iw01 - iw10 = -1
     (fractional offsets (0.00706080, 0.00132304) or (0.0000501, 0.2830146)):

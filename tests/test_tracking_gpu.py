@@ -150,6 +150,40 @@ def test_tracking_mirror_stagewise_parity(detector, features_to_track, colour):
     tr.close()
 
 
+def test_tracking_mirror_blank_frame_finds_no_model():
+    """A dropped camera frame (constant image, both sides) at frame 2 of a healthy
+    320x240 sequence: trackFrames keeps ~200 of the points on noise, solvePnPRansac
+    tries its 100 hypotheses and finds no model, so calculatePose marks every
+    feature an outlier and leaves the pose at the identity (R:src/tracking.cpp:189-229)
+    -- the step succeeds with 0 features. The next frame then has fewer than 4
+    points and raises (test_tracking_mirror_too_few_points_raises)."""
+    sc = Scene(320, 240, seed=3)
+    P0, P1 = sc.projections()
+    tr = Tracking(np.r_[P0.ravel(), P1.ravel()])
+    flat = np.full((240, 320), 128, np.uint8)
+    for t in range(2):
+        tr.push(sc.frame(t), sc.right(t))
+        assert tr.step()
+    assert tr.frame_info()["features"] > 300
+    tr.push(flat, flat)
+    assert tr.step()
+    obj, img = tr.trace("pnp_obj"), tr.trace("pnp_img")
+    rc, _, _, oinl, nh = O.solve_pnp_ransac(obj, img, sc.K)
+    assert len(img) >= 100 and rc == 0 and nh == 100 and len(oinl) == 0  # the oracle finds none on these inputs
+    pp = tr.trace("pnp_pose")
+    assert pp[6] == 0 and not np.any(pp[:6])
+    assert len(tr.trace("pnp_inliers")) == 0
+    info = tr.frame_info()
+    assert info["id"] == 2 and info["features"] == 0 and not info["keyframe"]
+    assert np.array_equal(info["R"], np.eye(3)) and not np.any(info["t"])
+    xy, world, _ = tr.features()
+    assert len(xy) == 0 and len(world) == 0
+    tr.push(sc.frame(3), sc.right(3))
+    with pytest.raises(S.SvoError):
+        tr.step()
+    tr.close()
+
+
 def test_tracking_mirror_too_few_points_raises():
     """calculatePose with < 4 points: OpenCV's CV_Assert throws; the mirror raises."""
     sc = Scene(320, 240, seed=2)
