@@ -108,6 +108,8 @@ public:
     [[nodiscard]] double inlierRatioValue() const { return inlierRatio; }
     [[nodiscard]] const SE3d& relativeMotion() const { return mRelativeMotion; }
     [[nodiscard]] svo_ctx* context() const { return mGpu; }
+    // K as calculatePose passes it (row-major 3x3): what Map::localBundleAdjust needs
+    [[nodiscard]] const double* intrinsics() const { return K; }
     void setTrace(TrackingTrace* trace) { mTrace = trace; }
 
 private:

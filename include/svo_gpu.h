@@ -240,6 +240,64 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
                      int max_n, const double K[9], double huber_delta, int max_iterations, double* poses,
                      double* costs, int* iterations);
 
+/* ------------------------------------------------------------ windowed bundle adjustment
+ * Poses and points together: the back end the reference promises (Map::run's
+ * "TODO optimization part here", R:src/map.cpp) and never builds. P problems,
+ * each with up to max_cams <= SVO_BA_MAX_CAMS cameras (poses: P*max_cams*12
+ * doubles, world -> camera as above; fixed: P*max_cams bytes, non-zero = held
+ * constant), up to max_points points (P*max_points*3 doubles) and up to max_obs
+ * monocular observations in any order (obs_cam / obs_point: indices within the
+ * problem, obs_xy: 2 floats). n_cams / n_points / n_obs: P counts each, or NULL
+ * = the maximum. Residual, Huber weight, cost and the Pz <= 0 rule per
+ * observation are those of svo_reprojection_jacobians. A point seen by fewer
+ * than two cameras in front of it is held constant (its observations still
+ * constrain their cameras), so is a point whose damped 3x3 block is not
+ * positive definite (for that iteration); a free camera with no observation in
+ * front of it is treated as fixed. Every stage runs on the device with a fixed
+ * summation order: the results do not depend on the order of the observations
+ * beyond a stable sort by (point, camera), and two runs give the same bits.
+ * SVO_ERR_ARG (nothing written): sizes or counts out of range, max_cams above
+ * SVO_BA_MAX_CAMS, an observation naming a camera or point outside its problem,
+ * NULL where data is required. */
+#define SVO_BA_MAX_CAMS 16
+/* Levenberg-Marquardt (svo_refine_poses' control: lambda from 1e-4, x0.1 down to
+ * 1e-12 on success, x10 on failure up to 1e16, the same stopping rules), per
+ * problem. poses, points: in/out. costs: P x 2 (initial, final), iterations: P
+ * (LM iterations each problem took); both may be NULL. */
+int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
+                      const int* n_points, const int* n_obs, double* poses, const uint8_t* fixed, double* points,
+                      const int* obs_cam, const int* obs_point, const float* obs_xy, const double K[9],
+                      double huber_delta, int max_iterations, double* costs, int* iterations);
+/* One linearisation and one solve at damping lambda, stage by stage (any output
+ * may be NULL). Per camera U (P*max_cams*21, upper triangle of sum w Jc^T Jc,
+ * row-major) and gc (6); per point V (P*max_points*6, upper triangle of sum w
+ * Jp^T Jp, Jp = Jc[:, :3] R) and gp (3); cost (P). The reduced system over the
+ * free cameras in index order, n = 6 n_free[p]: S (P x 6 max_cams x 6 max_cams,
+ * row-major, the leading n x n block, zero elsewhere) = U + lambda diag U - sum_i
+ * W_ij V*_i^-1 W_ik^T and b (P x 6 max_cams) = -gc + sum_i W_ij V*_i^-1 gp_i. The
+ * step: dc (P*max_cams*6, zero for cameras outside the reduced system), dp
+ * (P*max_points*3, zero for constant points); status (P): 1 = S not positive
+ * definite (dc and dp are zero). */
+int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
+                     const int* n_points, const int* n_obs, const double* poses, const uint8_t* fixed,
+                     const double* points, const int* obs_cam, const int* obs_point, const float* obs_xy,
+                     const double K[9], double huber_delta, double lambda, double* U, double* gc, double* V,
+                     double* gp, double* cost, double* S, double* b, double* dc, double* dp, int* n_free,
+                     int* status);
+/* The staging order of one problem's observations (host code, no GPU): the
+ * stable sort by (point, camera). order[k] = index of the k-th staged
+ * observation; pt_off (n_points + 1): point i owns staged positions
+ * [pt_off[i], pt_off[i + 1]); cam_idx[cam_off[j] .. cam_off[j + 1]) (cam_off:
+ * n_cams + 1): camera j's staged positions, ascending. */
+int svo_ba_sort_observations(const int* obs_cam, const int* obs_point, int n_obs, int n_cams, int n_points,
+                             int* order, int* pt_off, int* cam_off, int* cam_idx);
+/* One LM iteration's launch chain (linearise, eliminate, solve, update, trial
+ * cost) timed with HIP events: reps runs after one warm-up, ms per iteration. */
+int svo_ba_time_iteration(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
+                          const int* n_points, const int* n_obs, const double* poses, const uint8_t* fixed,
+                          const double* points, const int* obs_cam, const int* obs_point, const float* obs_xy,
+                          const double K[9], double huber_delta, double lambda, int reps, double* ms_per_iteration);
+
 /* ------------------------------------------------------------ batched front end
  * The reference's per-frame loop (Tracking::startStereo, R:src/tracking.cpp:232-276:
  * trackFrames -> calculatePose -> keyframe extractFeatures + findLeftFeaturesInRight

@@ -56,6 +56,20 @@ int svo_tracking_frame_info(const svo_tracking* tr, int64_t* frame_id, int* is_k
 /* Its left features: positions (2n floats), map point world positions (3n
  * doubles) and map point IDs (n); any output may be NULL. *n = count. */
 int svo_tracking_features(const svo_tracking* tr, float* xy, double* world, int64_t* mp_ids, int cap, int* n);
+/* Windowed bundle adjustment of the map (Map::localBundleAdjust over
+ * svo_bundle_adjust): the last `window` frames the map holds -- every frame but
+ * the newest, which Tracking still owns -- with the oldest n_fixed of them held
+ * constant, and the map points they observe. Never called by svo_tracking_step.
+ * costs: initial and final; iterations, counts (frames, points, observations
+ * taken) may be NULL. < 0 on error (message in last_error). */
+int svo_tracking_bundle_adjust(svo_tracking* tr, int window, int n_fixed, double huber_delta, int max_iterations,
+                               double costs[2], int* iterations, int64_t counts[3]);
+/* Frame `index` of the map in insertion order (negative: from the newest, -1):
+ * its ID, pose (camera -> world, as frame_info) and left features (as
+ * svo_tracking_features); any output may be NULL. Returns the number of frames
+ * the map holds, < 0 if there is no such frame. */
+int svo_tracking_map_frame(const svo_tracking* tr, int index, int64_t* frame_id, double pose[12], float* xy,
+                           double* world, int64_t* mp_ids, int cap, int* n);
 /* Per-stage trace of the last step. field: "lk_prev", "lk_next" (2 f32 per
  * point), "lk_status" (u8), "pnp_obj" (3 f64), "pnp_img" (2 f32),
  * "pnp_inliers" (i32), "pnp_pose" (rvec, tvec: 6 f64, then ok as f64),

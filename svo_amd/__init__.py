@@ -40,6 +40,7 @@ __all__ = [
 TERM_COUNT = 1
 TERM_EPS = 2
 LK_USE_INITIAL_FLOW = 4
+BA_MAX_CAMS = 16  # SVO_BA_MAX_CAMS: cameras of one bundle adjustment problem
 PYR_PAD = 32  # SVO_PYR_PAD: stored border of every pyramid level
 LK_GET_MIN_EIGENVALS = 8
 # SVO_LK_OPENCV_ORDER (not an OpenCV flag): LK's normal equations summed in OpenCV's
@@ -125,6 +126,14 @@ _SIGS = [
                                              C.c_double, _f64p, _f64p, _f64p]),
     ("svo_refine_poses", C.c_int, [_vp, _f64p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_double, C.c_int,
                                    _f64p, _f64p, _i32p]),
+    ("svo_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
+                                    _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_int, _f64p, _i32p]),
+    ("svo_ba_linearize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
+                                   _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
+                                   _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]),
+    ("svo_ba_sort_observations", C.c_int, [_i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p]),
+    ("svo_ba_time_iteration", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p,
+                                        _f64p, _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_double, C.c_int, _f64p]),
     ("svo_frontend_create", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     ("svo_frontend_destroy", None, [_vp]),
     ("svo_frontend_set_frame", C.c_int, [_vp, C.c_int, C.c_int, _u8p, _u8p, C.c_int]),
@@ -553,6 +562,84 @@ class Context:
                                            float(huber_delta), int(max_iterations), _p(poses, _f64p),
                                            _p(costs, _f64p), C.byref(it)))
         return poses, costs, it.value
+
+    # ---------------------------------------------------------------- bundle adjustment
+    @staticmethod
+    def _ba_args(poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs):
+        """One problem (poses (C, 12), points (M, 3), obs (O,)) or a batch (a leading
+        axis P on every array) -> the C ABI's arguments; (single, P, C, M, O, ...)."""
+        poses = np.array(poses, np.float64)
+        single = poses.ndim == 2
+        if single:
+            poses = poses[None]
+        P, Cn = poses.shape[0], poses.shape[1]
+        poses = np.ascontiguousarray(poses.reshape(P, Cn, 12))
+        points = np.array(points, np.float64)
+        obs_cam = np.asarray(obs_cam)
+        if single:
+            points, obs_cam = points[None], obs_cam[None]
+        Mn, On = points.shape[1], obs_cam.shape[1]
+        points = np.ascontiguousarray(points.reshape(P, Mn, 3))
+        fixed = _c(np.asarray(fixed, np.uint8).reshape(P, Cn), np.uint8)
+        obs_cam = _c(obs_cam.reshape(P, On), np.int32)
+        obs_point = _c(np.asarray(obs_point).reshape(P, On), np.int32)
+        obs_xy = _c(np.asarray(obs_xy).reshape(P, On, 2), np.float32)
+        K = _c(K, np.float64).reshape(9)
+        cnt = [None if c is None else _c(np.asarray(c).reshape(P), np.int32) for c in (n_cams, n_points, n_obs)]
+        return single, P, Cn, Mn, On, poses, fixed, points, obs_cam, obs_point, obs_xy, K, cnt
+
+    def bundle_adjust(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams=None, n_points=None,
+                      n_obs=None, huber_delta: float = 0.0, max_iterations: int = 50):
+        """Windowed bundle adjustment (svo_bundle_adjust): poses (P, C, 12) world ->
+        camera, fixed (P, C) bool, points (P, M, 3), observations obs_cam / obs_point
+        (P, O) and obs_xy (P, O, 2) in any order; n_cams / n_points / n_obs: (P,)
+        counts of a ragged batch. One problem may be given without the leading axis.
+        -> (poses, points, costs (P, 2): initial and final, iterations (P,))."""
+        single, P, Cn, Mn, On, poses, fixed, points, oc, op, oxy, K, cnt = self._ba_args(
+            poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs)
+        costs = np.zeros((P, 2), np.float64)
+        its = np.zeros(P, np.int32)
+        self._check(lib().svo_bundle_adjust(
+            self.handle, P, Cn, Mn, On, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
+            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), _p(K, _f64p),
+            float(huber_delta), int(max_iterations), _p(costs, _f64p), _p(its, _i32p)))
+        if single:
+            return poses[0], points[0], costs[0], int(its[0])
+        return poses, points, costs, its
+
+    def ba_linearize(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, lam: float = 1e-4, n_cams=None,
+                     n_points=None, n_obs=None, huber_delta: float = 0.0) -> dict:
+        """One linearisation and one solve of the bundle adjustment at damping lam
+        (svo_ba_linearize) -> dict of U (P, C, 21), gc (P, C, 6), V (P, M, 6), gp
+        (P, M, 3), cost (P,), S (P, 6C, 6C), b (P, 6C), dc (P, C, 6), dp (P, M, 3),
+        n_free (P,), status (P,); without the leading axis for one problem."""
+        single, P, Cn, Mn, On, poses, fixed, points, oc, op, oxy, K, cnt = self._ba_args(
+            poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs)
+        out = {"U": np.zeros((P, Cn, 21)), "gc": np.zeros((P, Cn, 6)), "V": np.zeros((P, Mn, 6)),
+               "gp": np.zeros((P, Mn, 3)), "cost": np.zeros(P), "S": np.zeros((P, 6 * Cn, 6 * Cn)),
+               "b": np.zeros((P, 6 * Cn)), "dc": np.zeros((P, Cn, 6)), "dp": np.zeros((P, Mn, 3))}
+        nfree = np.zeros(P, np.int32)
+        status = np.zeros(P, np.int32)
+        self._check(lib().svo_ba_linearize(
+            self.handle, P, Cn, Mn, On, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
+            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), _p(K, _f64p),
+            float(huber_delta), float(lam), *[_p(out[k], _f64p) for k in ("U", "gc", "V", "gp", "cost", "S", "b",
+                                                                          "dc", "dp")],
+            _p(nfree, _i32p), _p(status, _i32p)))
+        out["n_free"], out["status"] = nfree, status
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def ba_time_iteration(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, lam: float = 1e-4,
+                          n_cams=None, n_points=None, n_obs=None, huber_delta: float = 0.0, reps: int = 10) -> float:
+        """ms per LM iteration of the bundle adjustment's launch chain (HIP events)."""
+        _, P, Cn, Mn, On, poses, fixed, points, oc, op, oxy, K, cnt = self._ba_args(
+            poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs)
+        ms = C.c_double()
+        self._check(lib().svo_ba_time_iteration(
+            self.handle, P, Cn, Mn, On, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p), _p(fixed, _u8p), _p(points, _f64p),
+            _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), _p(K, _f64p), float(huber_delta), float(lam), int(reps),
+            C.byref(ms)))
+        return ms.value
 
     def solve_pnp_ransac(self, obj, img_pts, K, iterations: int = 100, reproj_err: float = 8.0,
                          confidence: float = 0.999):

@@ -1,0 +1,609 @@
+// Windowed bundle adjustment: poses and points together.
+// A problem has C <= SVO_BA_MAX_CAMS cameras (world -> camera, 12 doubles,
+// reproj.hip's conventions), M points and O monocular observations (camera,
+// point, u, v). Per observation the residual, Huber weight, cost, Pz <= 0 rule
+// and pose Jacobian Jc (2x6, left perturbation) are reproj_kernel's; the point
+// Jacobian is Jp = Jc[:, :3] R (2x3). One Levenberg-Marquardt iteration:
+//   1 linearise   U_j = sum w Jc^T Jc, gc_j, cost (per camera); V_i = sum w Jp^T Jp,
+//                 gp_i (per point); W_ij = w Jc^T Jp is recomputed where it is used
+//   2 eliminate   V*_i = V_i + lambda diag V_i inverted in closed form,
+//                 S = U* - sum_i W_ij V*_i^-1 W_ik^T, b = -gc + sum_i W_ij V*_i^-1 gp_i
+//   3 solve       S dc = b by Cholesky, packed lower triangle in LDS
+//   4 update      dp_i = V*_i^-1 (-gp_i - sum_j W_ij^T dc_j); trial points and poses
+//   5 cost        of the trial state (stage 1's camera pass, cost only)
+// Every sum has a fixed order (a thread's own items in index order, wave
+// shuffles, LDS, then partials in index order) and nothing is accumulated with
+// atomics, so two runs give the same bits. Points seen by fewer than two cameras
+// in front of them, and points whose damped block is not positive definite, are
+// held constant; a free camera with no observation in front of it is treated as
+// fixed.
+#include "ba.hpp"
+
+namespace svo {
+
+namespace {
+
+constexpr int kMaxCams = SVO_BA_MAX_CAMS;
+constexpr int kMaxN = 6 * kMaxCams;               // reduced system order
+constexpr int kMaxNS = kMaxN * (kMaxN + 1) / 2;   // packed lower triangle
+constexpr int kSolveThreads = 512;
+constexpr int kEPT = (kMaxNS + kSolveThreads - 1) / kSolveThreads;  // S entries per thread
+constexpr int kPT = 4;                            // points staged per pass of the elimination
+constexpr int kWStride = kMaxCams * 18;           // doubles of W (or Y) per staged point
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct Cam {
+    double fx, fy, cx, cy, delta;
+};
+
+// reproj_kernel's residual, Jacobian, weight and cost; false (nothing written)
+// when the point is not in front of the camera
+__device__ __forceinline__ bool obs_eval(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
+                                         const float* __restrict__ u, double& r0, double& r1, double& w, double& cost,
+                                         double J[12]) {
+    const double px = T[0] * X[0] + T[1] * X[1] + T[2] * X[2] + T[9];
+    const double py = T[3] * X[0] + T[4] * X[1] + T[5] * X[2] + T[10];
+    const double pz = T[6] * X[0] + T[7] * X[1] + T[8] * X[2] + T[11];
+    if (!(pz > 0)) return false;
+    const double iz = 1.0 / pz, x = px * iz, y = py * iz;
+    r0 = k.fx * x + k.cx - (double)u[0];
+    r1 = k.fy * y + k.cy - (double)u[1];
+    J[0] = k.fx * iz;
+    J[1] = 0;
+    J[2] = -k.fx * x * iz;
+    J[3] = -k.fx * x * y;
+    J[4] = k.fx * (1 + x * x);
+    J[5] = -k.fx * y;
+    J[6] = 0;
+    J[7] = k.fy * iz;
+    J[8] = -k.fy * y * iz;
+    J[9] = -k.fy * (1 + y * y);
+    J[10] = k.fy * x * y;
+    J[11] = k.fy * x;
+    const double nr = sqrt(r0 * r0 + r1 * r1);
+    const bool robust = k.delta > 0 && nr > k.delta;
+    w = robust ? k.delta / nr : 1.0;
+    cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * (r0 * r0 + r1 * r1);
+    return true;
+}
+
+// Jp = Jc[:, :3] R (row a of Jp at Jp[3 a])
+__device__ __forceinline__ void point_jacobian(const double J[12], const double* __restrict__ T, double Jp[6]) {
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) Jp[3 * a + c] = J[6 * a] * T[c] + J[6 * a + 1] * T[3 + c] + J[6 * a + 2] * T[6 + c];
+}
+
+// ------------------------------------------------------------------ stage 1 / 5: per camera
+// One block per (camera, problem); thread t takes the camera's observations
+// t, t + 256, ... in order. kFull: U, gc, cost and the in-front count; else the
+// cost alone.
+template <bool kFull>
+__global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double* __restrict__ poses,
+                                                        const double* __restrict__ points) {
+    constexpr int kN = kFull ? kBaNE : 1;
+    const int p = blockIdx.y, j = blockIdx.x;
+    if (!d.active[p] || j >= d.n_cams[p]) return;
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const double* T = poses + 12 * ((size_t)p * d.maxC + j);
+    const size_t ob = (size_t)p * d.maxO;
+    const int o0 = d.cam_off[(size_t)p * (d.maxC + 1) + j], o1 = d.cam_off[(size_t)p * (d.maxC + 1) + j + 1];
+    double e[kN];
+#pragma unroll
+    for (int q = 0; q < kN; q++) e[q] = 0;
+    int cnt = 0;
+    for (int a = o0 + (int)threadIdx.x; a < o1; a += 256) {
+        const int o = d.cam_idx[ob + a];
+        const double* X = points + 3 * ((size_t)p * d.maxM + d.cam_pt[ob + a]);
+        double r0, r1, w, c, J[12];
+        if (!obs_eval(k, T, X, d.oxy + 2 * (ob + o), r0, r1, w, c, J)) continue;
+        cnt++;
+        if (kFull) {
+            int q = 0;
+#pragma unroll
+            for (int a2 = 0; a2 < 6; a2++)
+#pragma unroll
+                for (int c2 = a2; c2 < 6; c2++) e[q++] += w * (J[a2] * J[c2] + J[6 + a2] * J[6 + c2]);
+#pragma unroll
+            for (int a2 = 0; a2 < 6; a2++) e[21 + a2] += w * (J[a2] * r0 + J[6 + a2] * r1);
+        }
+        e[kN - 1] += c;
+    }
+    __shared__ double S[4][kN];
+    __shared__ int Sc[4];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int q = 0; q < kN; q++) {
+        const double s = wave_sum(e[q]);
+        if (lane == 0) S[wv][q] = s;
+    }
+    const int cs = wave_sum_int(cnt);
+    if (lane == 0) Sc[wv] = cs;
+    __syncthreads();
+    const size_t cj = (size_t)p * d.maxC + j;
+    if ((int)threadIdx.x < kN) {
+        const int q = threadIdx.x;
+        const double s = ((S[0][q] + S[1][q]) + S[2][q]) + S[3][q];
+        if (kFull)
+            d.cam_ne[cj * kBaNE + q] = s;
+        else
+            d.cam_cost[cj] = s;
+    }
+    if (kFull && threadIdx.x == 0) d.cam_cnt[cj] = Sc[0] + Sc[1] + Sc[2] + Sc[3];
+}
+
+// cost[p] = sum over the cameras, in index order, of src[(p maxC + j) stride + off]
+__global__ void ba_cost_sum_kernel(BaBatch d, const double* __restrict__ src, int stride, int off,
+                                   double* __restrict__ cost) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= d.P || !d.active[p]) return;
+    double s = 0;
+    for (int j = 0; j < d.n_cams[p]; j++) s += src[((size_t)p * d.maxC + j) * stride + off];
+    cost[p] = s;
+}
+
+// ------------------------------------------------------------------ stage 1 / 2: per point
+// One thread per point: V, gp over its observations in camera order, then the
+// damped block's inverse by cofactors.
+__global__ __launch_bounds__(256) void ba_point_kernel(BaBatch d, const double* __restrict__ poses,
+                                                       const double* __restrict__ points) {
+    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (!d.active[p] || i >= d.n_points[p]) return;
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const size_t ob = (size_t)p * d.maxO, pi = (size_t)p * d.maxM + i;
+    const double* X = points + 3 * pi;
+    const int o0 = d.pt_off[(size_t)p * (d.maxM + 1) + i], o1 = d.pt_off[(size_t)p * (d.maxM + 1) + i + 1];
+    double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+    int nfront = 0;
+    for (int a = o0; a < o1; a++) {
+        const double* T = poses + 12 * ((size_t)p * d.maxC + d.ocam[ob + a]);
+        double r0, r1, w, c, J[12], Jp[6];
+        if (!obs_eval(k, T, X, d.oxy + 2 * (ob + a), r0, r1, w, c, J)) continue;
+        nfront++;
+        point_jacobian(J, T, Jp);
+        int q = 0;
+#pragma unroll
+        for (int s = 0; s < 3; s++)
+#pragma unroll
+            for (int t = s; t < 3; t++) V[q++] += w * (Jp[s] * Jp[t] + Jp[3 + s] * Jp[3 + t]);
+#pragma unroll
+        for (int s = 0; s < 3; s++) g[s] += w * (Jp[s] * r0 + Jp[3 + s] * r1);
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) d.pt_V[6 * pi + q] = V[q];
+#pragma unroll
+    for (int q = 0; q < 3; q++) d.pt_g[3 * pi + q] = g[q];
+    const double lam = d.lambda[p];
+    const double a = V[0] + lam * V[0], b = V[1], c = V[2], dd = V[3] + lam * V[3], e = V[4], f = V[5] + lam * V[5];
+    const double c00 = dd * f - e * e, c01 = c * e - b * f, c02 = b * e - c * dd;
+    const double c11 = a * f - c * c, c12 = b * c - a * e, c22 = a * dd - b * b;
+    const double det = (a * c00 + b * c01) + c * c02;
+    const bool ok = nfront >= 2 && a > 0 && c22 > 0 && det > 0;
+    const double id = ok ? 1.0 / det : 0.0;
+    d.pt_Vinv[6 * pi + 0] = c00 * id;
+    d.pt_Vinv[6 * pi + 1] = c01 * id;
+    d.pt_Vinv[6 * pi + 2] = c02 * id;
+    d.pt_Vinv[6 * pi + 3] = c11 * id;
+    d.pt_Vinv[6 * pi + 4] = c12 * id;
+    d.pt_Vinv[6 * pi + 5] = c22 * id;
+    d.pt_free[pi] = ok ? 1 : 0;
+}
+
+// W_ij = sum over point i's observations by camera `cam` of w Jc^T Jp (6x3, row-major)
+__device__ __forceinline__ void accumulate_W(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
+                                             const float* __restrict__ u, double W[18]) {
+    double r0, r1, w, c, J[12], Jp[6];
+    if (!obs_eval(k, T, X, u, r0, r1, w, c, J)) return;
+    point_jacobian(J, T, Jp);
+#pragma unroll
+    for (int x = 0; x < 6; x++)
+#pragma unroll
+        for (int t = 0; t < 3; t++) W[3 * x + t] += w * (J[x] * Jp[t] + J[6 + x] * Jp[3 + t]);
+}
+
+__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
+
+// ------------------------------------------------------------------ stages 2 + 3
+// One workgroup per problem. Thread t owns the packed entries t, t + 512, ... of
+// S in registers while the points stream through LDS kPT at a time: one lane per
+// observation of those points stages W_ij and Y_ij = W_ij V*_i^-1 (zero where the
+// camera does not see the point or the point is constant), then every thread
+// subtracts Y_ij W_ik^T from its entries, points in index order. The assembled
+// system is factored and solved in LDS.
+__global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d, const double* __restrict__ poses,
+                                                                       const double* __restrict__ points,
+                                                                       double* __restrict__ S_out,
+                                                                       double* __restrict__ b_out) {
+    const int p = blockIdx.x, t = threadIdx.x;
+    if (!d.active[p]) return;
+    __shared__ double Sl[kMaxNS];
+    __shared__ double Wl[kPT * kWStride], Yl[kPT * kWStride];
+    __shared__ double gpl[kPT * 3];
+    __shared__ double bl[kMaxN];
+    __shared__ int freecam[kMaxCams], camslot[kMaxCams];  // free index -> camera and back (-1: not free)
+    __shared__ int soff[kPT + 1], slive[kPT];
+    __shared__ int s_nfree;
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const int C = d.n_cams[p], M = d.n_points[p];
+    const size_t cb = (size_t)p * d.maxC, ob = (size_t)p * d.maxO, pb = (size_t)p * d.maxM;
+    if (t == 0) {
+        int nf = 0;
+        for (int j = 0; j < kMaxCams; j++) camslot[j] = -1;
+        for (int j = 0; j < C; j++)
+            if (!d.fixed[cb + j] && d.cam_cnt[cb + j] > 0) {
+                camslot[j] = nf;
+                freecam[nf++] = j;
+            }
+        s_nfree = nf;
+        d.n_free[p] = nf;
+        d.status[p] = 0;
+    }
+    for (int q = t; q < 6 * d.maxC; q += kSolveThreads) d.dc[6 * cb + q] = 0;
+    __syncthreads();
+    const int nf = s_nfree, n = 6 * nf, NS = n * (n + 1) / 2;
+    if (n == 0) return;
+    const double lam = d.lambda[p];
+
+    // this thread's entries: LDS offsets of the Y row and the W row, and U* as the start
+    int offY[kEPT], offW[kEPT];
+    double acc[kEPT];
+#pragma unroll
+    for (int q = 0; q < kEPT; q++) {
+        const int e = t + q * kSolveThreads;
+        offY[q] = offW[q] = 0;
+        acc[q] = 0;
+        if (e < NS) {
+            int r = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+            while (tri(r, 0) > e) r--;
+            while (tri(r + 1, 0) <= e) r++;
+            const int c = e - tri(r, 0);
+            const int jr = r / 6, x = r - 6 * jr, jc = c / 6, y = c - 6 * jc;
+            offY[q] = jr * 18 + x * 3;
+            offW[q] = jc * 18 + y * 3;
+            if (jr == jc) {  // y <= x: entry (y, x) of the upper triangle of U
+                const double u = d.cam_ne[(cb + freecam[jr]) * kBaNE + (y * 6 - y * (y - 1) / 2 + (x - y))];
+                acc[q] = r == c ? u + lam * u : u;
+            }
+        }
+    }
+    double accb = 0;
+    const int offB = t < n ? (t / 6) * 18 + (t % 6) * 3 : 0;
+
+    for (int base = 0; base < M; base += kPT) {
+        // clear the staging area; the first kPT + 1 lanes fetch the points' runs, flags and gp
+        for (int z = t; z < kPT * kWStride; z += kSolveThreads) Wl[z] = Yl[z] = 0;
+        if (t <= kPT) {
+            const int i = base + t < M ? base + t : M;
+            soff[t] = d.pt_off[(size_t)p * (d.maxM + 1) + i];
+            if (t < kPT) {
+                const bool live = base + t < M && d.pt_free[pb + i] != 0;
+                slive[t] = live;
+#pragma unroll
+                for (int z = 0; z < 3; z++) gpl[3 * t + z] = live ? d.pt_g[3 * (pb + i) + z] : 0.0;
+            }
+        }
+        __syncthreads();
+        // one lane per staged observation of these points (their runs are contiguous);
+        // the first observation of a (point, camera) run sums the run and owns the slot
+        for (int a = soff[0] + t; a < soff[kPT]; a += kSolveThreads) {
+            int q = 0;
+#pragma unroll
+            for (int z = 1; z < kPT; z++) q += a >= soff[z];
+            const int cam = d.ocam[ob + a], jf = camslot[cam];
+            if (jf < 0 || !slive[q] || (a > soff[q] && d.ocam[ob + a - 1] == cam)) continue;
+            const int i = base + q;
+            const double* T = poses + 12 * (cb + cam);
+            const double* X = points + 3 * (pb + i);
+            double W[18];
+#pragma unroll
+            for (int z = 0; z < 18; z++) W[z] = 0;
+            for (int a2 = a; a2 < soff[q + 1] && d.ocam[ob + a2] == cam; a2++)
+                accumulate_W(k, T, X, d.oxy + 2 * (ob + a2), W);
+            const double* Vi = d.pt_Vinv + 6 * (pb + i);
+            const double v00 = Vi[0], v01 = Vi[1], v02 = Vi[2], v11 = Vi[3], v12 = Vi[4], v22 = Vi[5];
+            double* Wo = Wl + q * kWStride + jf * 18;
+            double* Yo = Yl + q * kWStride + jf * 18;
+#pragma unroll
+            for (int x = 0; x < 6; x++) {
+                Wo[3 * x] = W[3 * x];
+                Wo[3 * x + 1] = W[3 * x + 1];
+                Wo[3 * x + 2] = W[3 * x + 2];
+                Yo[3 * x + 0] = (W[3 * x] * v00 + W[3 * x + 1] * v01) + W[3 * x + 2] * v02;
+                Yo[3 * x + 1] = (W[3 * x] * v01 + W[3 * x + 1] * v11) + W[3 * x + 2] * v12;
+                Yo[3 * x + 2] = (W[3 * x] * v02 + W[3 * x + 1] * v12) + W[3 * x + 2] * v22;
+            }
+        }
+        __syncthreads();
+        // one staged point at a time: unrolled over the points as well, the
+        // compiler hoists every LDS read of the pass and spills
+#pragma unroll 1
+        for (int s = 0; s < kPT; s++)
+#pragma unroll
+            for (int q = 0; q < kEPT; q++) {
+                const double* Yr = Yl + s * kWStride + offY[q];
+                const double* Wr = Wl + s * kWStride + offW[q];
+                acc[q] -= Yr[0] * Wr[0];
+                acc[q] -= Yr[1] * Wr[1];
+                acc[q] -= Yr[2] * Wr[2];
+            }
+        if (t < n)
+#pragma unroll
+            for (int s = 0; s < kPT; s++) {
+                const double* Yr = Yl + s * kWStride + offB;
+                accb += Yr[0] * gpl[3 * s];
+                accb += Yr[1] * gpl[3 * s + 1];
+                accb += Yr[2] * gpl[3 * s + 2];
+            }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int q = 0; q < kEPT; q++) {
+        const int e = t + q * kSolveThreads;
+        if (e < NS) Sl[e] = acc[q];
+    }
+    if (t < n) bl[t] = accb - d.cam_ne[(cb + freecam[t / 6]) * kBaNE + 21 + t % 6];
+    __syncthreads();
+    if (S_out) {
+        const int ld = 6 * d.maxC;
+        double* So = S_out + (size_t)p * ld * ld;
+        for (int q = t; q < n * n; q += kSolveThreads) {
+            const int r = q / n, c = q - r * n;
+            So[(size_t)r * ld + c] = r >= c ? Sl[tri(r, c)] : Sl[tri(c, r)];
+        }
+    }
+    if (b_out && t < n) b_out[(size_t)p * 6 * d.maxC + t] = bl[t];
+    __syncthreads();
+
+    // Cholesky S = L L^T, column by column: thread i owns row i
+    bool bad = false;
+    for (int j = 0; j < n; j++) {
+        double s = 0;
+        if (t >= j && t < n) {
+            s = Sl[tri(t, j)];
+            for (int q = 0; q < j; q++) s -= Sl[tri(t, q)] * Sl[tri(j, q)];
+            Sl[tri(t, j)] = s;
+        }
+        __syncthreads();
+        const double dj = Sl[tri(j, j)];
+        __syncthreads();
+        if (!(dj > 0)) {
+            bad = true;
+            break;
+        }
+        if (t >= j && t < n) Sl[tri(t, j)] = t == j ? sqrt(dj) : s / sqrt(dj);
+        __syncthreads();
+    }
+    if (bad) {
+        if (t == 0) d.status[p] = 1;
+        return;
+    }
+    for (int j = 0; j < n; j++) {  // L y = b
+        if (t == j) bl[j] = bl[j] / Sl[tri(j, j)];
+        __syncthreads();
+        if (t > j && t < n) bl[t] -= Sl[tri(t, j)] * bl[j];
+        __syncthreads();
+    }
+    for (int j = n - 1; j >= 0; j--) {  // L^T x = y
+        if (t == j) bl[j] = bl[j] / Sl[tri(j, j)];
+        __syncthreads();
+        if (t < j) bl[t] -= Sl[tri(j, t)] * bl[j];
+        __syncthreads();
+    }
+    if (t < n) d.dc[6 * (cb + freecam[t / 6]) + t % 6] = bl[t];
+}
+
+// ------------------------------------------------------------------ stage 4: points
+__global__ __launch_bounds__(256) void ba_point_update_kernel(BaBatch d, const double* __restrict__ poses,
+                                                              const double* __restrict__ points,
+                                                              double* __restrict__ trial_points,
+                                                              double* __restrict__ dp_out) {
+    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (!d.active[p]) return;
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const size_t cb = (size_t)p * d.maxC, ob = (size_t)p * d.maxO, pi = (size_t)p * d.maxM + i;
+    double sd = 0, sx = 0;
+    if (i < d.n_points[p]) {
+        const double X[3] = {points[3 * pi], points[3 * pi + 1], points[3 * pi + 2]};
+        double dp[3] = {0, 0, 0};
+        const bool moves = d.status[p] == 0 && d.pt_free[pi] != 0;
+        if (moves) {
+            double a3[3] = {-d.pt_g[3 * pi], -d.pt_g[3 * pi + 1], -d.pt_g[3 * pi + 2]};
+            const int o0 = d.pt_off[(size_t)p * (d.maxM + 1) + i], o1 = d.pt_off[(size_t)p * (d.maxM + 1) + i + 1];
+            for (int a = o0; a < o1; a++) {
+                const int cam = d.ocam[ob + a];
+                if (d.fixed[cb + cam]) continue;
+                double W[18];
+#pragma unroll
+                for (int z = 0; z < 18; z++) W[z] = 0;
+                accumulate_W(k, poses + 12 * (cb + cam), X, d.oxy + 2 * (ob + a), W);
+                const double* dc = d.dc + 6 * (cb + cam);
+#pragma unroll
+                for (int s = 0; s < 3; s++)
+#pragma unroll
+                    for (int x = 0; x < 6; x++) a3[s] -= W[3 * x + s] * dc[x];
+            }
+            const double* Vi = d.pt_Vinv + 6 * pi;
+            dp[0] = (Vi[0] * a3[0] + Vi[1] * a3[1]) + Vi[2] * a3[2];
+            dp[1] = (Vi[1] * a3[0] + Vi[3] * a3[1]) + Vi[4] * a3[2];
+            dp[2] = (Vi[2] * a3[0] + Vi[4] * a3[1]) + Vi[5] * a3[2];
+            sd = (dp[0] * dp[0] + dp[1] * dp[1]) + dp[2] * dp[2];
+            sx = (X[0] * X[0] + X[1] * X[1]) + X[2] * X[2];
+        }
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+            trial_points[3 * pi + s] = moves ? X[s] + dp[s] : X[s];
+            if (dp_out) dp_out[3 * pi + s] = dp[s];
+        }
+    }
+    __shared__ double S[4][2];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    sd = wave_sum(sd);
+    sx = wave_sum(sx);
+    if (lane == 0) {
+        S[wv][0] = sd;
+        S[wv][1] = sx;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int q = threadIdx.x;
+        d.step_part[((size_t)p * gridDim.x + blockIdx.x) * 2 + q] = ((S[0][q] + S[1][q]) + S[2][q]) + S[3][q];
+    }
+}
+
+// T <- exp(xi^) T, xi = (rho, phi): refine.cpp's se3_left_update
+__device__ void se3_left_update(const double xi[6], const double* __restrict__ T, double* __restrict__ out) {
+    const double* rho = xi;
+    const double* ph = xi + 3;
+    const double th2 = (ph[0] * ph[0] + ph[1] * ph[1]) + ph[2] * ph[2];
+    const double th = sqrt(th2);
+    double A, B, Cc;  // sin/th, (1-cos)/th^2, (th-sin)/th^3
+    if (th < 1e-8) {
+        A = 1 - th2 / 6;
+        B = 0.5 - th2 / 24;
+        Cc = 1.0 / 6 - th2 / 120;
+    } else {
+        A = sin(th) / th;
+        B = (1 - cos(th)) / th2;
+        Cc = (th - sin(th)) / (th2 * th);
+    }
+    const double W[9] = {0, -ph[2], ph[1], ph[2], 0, -ph[0], -ph[1], ph[0], 0};
+    double W2[9], R[9], V[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) W2[3 * i + j] = (W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j]) + W[3 * i + 2] * W[6 + j];
+#pragma unroll
+    for (int q = 0; q < 9; q++) {
+        const double I = (q % 4 == 0);
+        R[q] = (I + A * W[q]) + B * W2[q];
+        V[q] = (I + B * W[q]) + Cc * W2[q];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double tx = (V[3 * i] * rho[0] + V[3 * i + 1] * rho[1]) + V[3 * i + 2] * rho[2];
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[3 * i + j] = (R[3 * i] * T[j] + R[3 * i + 1] * T[3 + j]) + R[3 * i + 2] * T[6 + j];
+        out[9 + i] = ((R[3 * i] * T[9] + R[3 * i + 1] * T[10]) + R[3 * i + 2] * T[11]) + tx;
+    }
+}
+
+// ------------------------------------------------------------------ stage 4: poses, step size
+// One wave per problem: lane j moves camera j; lane 0 then sums the step and
+// state norms, cameras and point blocks in index order.
+__global__ __launch_bounds__(64) void ba_pose_update_kernel(BaBatch d, const double* __restrict__ poses,
+                                                            double* __restrict__ trial_poses, int nblk) {
+    const int p = blockIdx.x, j = threadIdx.x;
+    if (!d.active[p]) return;
+    const size_t cb = (size_t)p * d.maxC;
+    const int C = d.n_cams[p];
+    __shared__ double nrm[kMaxCams][2];
+    if (j < kMaxCams) nrm[j][0] = nrm[j][1] = 0;
+    if (j < C) {
+        const double* T = poses + 12 * (cb + j);
+        double* out = trial_poses + 12 * (cb + j);
+        const bool moves = d.status[p] == 0 && !d.fixed[cb + j] && d.cam_cnt[cb + j] > 0;
+        if (moves) {
+            double xi[6];
+#pragma unroll
+            for (int q = 0; q < 6; q++) xi[q] = d.dc[6 * (cb + j) + q];
+            se3_left_update(xi, T, out);
+            double s = 0;
+#pragma unroll
+            for (int q = 0; q < 6; q++) s += xi[q] * xi[q];
+            nrm[j][0] = s;
+            nrm[j][1] = (T[9] * T[9] + T[10] * T[10]) + T[11] * T[11];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 12; q++) out[q] = T[q];
+        }
+    }
+    __syncthreads();
+    if (j == 0) {
+        double s0 = 0, s1 = 0;
+        for (int q = 0; q < C; q++) {
+            s0 += nrm[q][0];
+            s1 += nrm[q][1];
+        }
+        for (int q = 0; q < nblk; q++) {
+            s0 += d.step_part[((size_t)p * nblk + q) * 2];
+            s1 += d.step_part[((size_t)p * nblk + q) * 2 + 1];
+        }
+        d.stepinfo[2 * p] = s0;
+        d.stepinfo[2 * p + 1] = s1;
+    }
+}
+
+__global__ __launch_bounds__(256) void ba_commit_kernel(BaBatch d, const int* __restrict__ accept,
+                                                        const double* __restrict__ trial_poses,
+                                                        const double* __restrict__ trial_points,
+                                                        double* __restrict__ poses, double* __restrict__ points) {
+    const int p = blockIdx.y;
+    if (!accept[p]) return;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int nc = 12 * d.n_cams[p], np = 3 * d.n_points[p];
+    if (q < nc) poses[12 * (size_t)p * d.maxC + q] = trial_poses[12 * (size_t)p * d.maxC + q];
+    if (q < np) points[3 * (size_t)p * d.maxM + q] = trial_points[3 * (size_t)p * d.maxM + q];
+}
+
+}  // namespace
+
+int ba_point_blocks(int max_points) { return max_points > 0 ? (max_points + 255) / 256 : 1; }
+
+hipError_t launch_ba_linearize(const BaBatch& b, const double* poses, const double* points, hipStream_t st) {
+    if (b.P <= 0) return hipSuccess;
+    if (b.maxC > 0)
+        hipLaunchKernelGGL(ba_camera_kernel<true>, dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+    if (b.maxM > 0)
+        hipLaunchKernelGGL(ba_point_kernel, dim3((b.maxM + 255) / 256, b.P), dim3(256), 0, st, b, poses, points);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_schur_solve(const BaBatch& b, const double* poses, const double* points, double* S_out,
+                                 double* b_out, hipStream_t st) {
+    if (b.P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ba_schur_solve_kernel, dim3(b.P), dim3(kSolveThreads), 0, st, b, poses, points, S_out, b_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_update(const BaBatch& b, const double* poses, const double* points, double* trial_poses,
+                            double* trial_points, double* dp_out, hipStream_t st) {
+    if (b.P <= 0) return hipSuccess;
+    const int nblk = ba_point_blocks(b.maxM);
+    hipLaunchKernelGGL(ba_point_update_kernel, dim3(nblk, b.P), dim3(256), 0, st, b, poses, points, trial_points,
+                       dp_out);
+    hipLaunchKernelGGL(ba_pose_update_kernel, dim3(b.P), dim3(64), 0, st, b, poses, trial_poses, nblk);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_cost(const BaBatch& b, const double* poses, const double* points, double* cost, hipStream_t st) {
+    if (b.P <= 0) return hipSuccess;
+    if (b.maxC > 0)
+        hipLaunchKernelGGL(ba_camera_kernel<false>, dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+    hipLaunchKernelGGL(ba_cost_sum_kernel, dim3((b.P + 255) / 256), dim3(256), 0, st, b, b.cam_cost, 1, 0, cost);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_commit(const BaBatch& b, const int* accept, const double* trial_poses,
+                            const double* trial_points, double* poses, double* points, hipStream_t st) {
+    if (b.P <= 0) return hipSuccess;
+    const int most = 12 * b.maxC > 3 * b.maxM ? 12 * b.maxC : 3 * b.maxM;
+    if (most <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ba_commit_kernel, dim3((most + 255) / 256, b.P), dim3(256), 0, st, b, accept, trial_poses,
+                       trial_points, poses, points);
+    return hipGetLastError();
+}
+
+}  // namespace svo

@@ -123,10 +123,62 @@ int svo_tracking_frame_info(const svo_tracking* tr, int64_t* frame_id, int* is_k
     return 0;
 }
 
+namespace {
+
+void copy_features(const svo::StereoFrame* f, float* xy, double* world, int64_t* mp_ids, int cap, int* n);
+
+}  // namespace
+
 int svo_tracking_features(const svo_tracking* tr, float* xy, double* world, int64_t* mp_ids, int cap, int* n) {
     if (!tr || !tr->tracking || cap < 0) return -1;
     svo::StereoFrame* f = tr->tracking->lastFrame();
     if (!f) return -1;
+    copy_features(f, xy, world, mp_ids, cap, n);
+    return 0;
+}
+
+int svo_tracking_bundle_adjust(svo_tracking* tr, int window, int n_fixed, double huber_delta, int max_iterations,
+                               double costs[2], int* iterations, int64_t counts[3]) {
+    if (!tr || !tr->tracking) return -1;
+    try {
+        const svo::Map::BundleResult r = tr->map.localBundleAdjust(
+            tr->tracking->context(), tr->tracking->intrinsics(), window, n_fixed, huber_delta, max_iterations);
+        if (costs) {
+            costs[0] = r.initialCost;
+            costs[1] = r.finalCost;
+        }
+        if (iterations) *iterations = r.iterations;
+        if (counts) {
+            counts[0] = (int64_t)r.frames;
+            counts[1] = (int64_t)r.points;
+            counts[2] = (int64_t)r.observations;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        tr->err = e.what();
+        return -2;
+    }
+}
+
+int svo_tracking_map_frame(const svo_tracking* tr, int index, int64_t* frame_id, double pose[12], float* xy,
+                           double* world, int64_t* mp_ids, int cap, int* n) {
+    if (!tr || cap < 0) return -1;
+    auto* f = dynamic_cast<svo::StereoFrame*>(tr->map.frameAt(index));
+    if (!f) return -1;
+    if (frame_id) *frame_id = (int64_t)f->ID;
+    if (pose) {
+        std::memcpy(pose, f->pose().R, sizeof(double) * 9);
+        std::memcpy(pose + 9, f->pose().t, sizeof(double) * 3);
+    }
+    copy_features(f, xy, world, mp_ids, cap, n);
+    return (int)tr->map.framesSize();
+}
+
+}  // extern "C"
+
+namespace {
+
+void copy_features(const svo::StereoFrame* f, float* xy, double* world, int64_t* mp_ids, int cap, int* n) {
     const auto& fs = f->leftFeatures();
     if (n) *n = (int)fs.size();
     for (size_t i = 0; i < fs.size() && (int)i < cap; i++) {
@@ -142,8 +194,11 @@ int svo_tracking_features(const svo_tracking* tr, float* xy, double* world, int6
         }
         if (mp_ids) mp_ids[i] = mp ? (int64_t)mp->ID : -1;
     }
-    return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 int64_t svo_tracking_trace(const svo_tracking* tr, const char* field, void* dst, int64_t cap) {
     if (!tr || !field) return -1;

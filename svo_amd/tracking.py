@@ -40,6 +40,8 @@ _SIGS = [
     ("svo_tracking_step", C.c_int, [_vp]),
     ("svo_tracking_frame_info", C.c_int, [_vp, _i64p, _i32p, _i64p, _i64p, _f64p, _f64p]),
     ("svo_tracking_features", C.c_int, [_vp, _f32p, _f64p, _i64p, C.c_int, _i32p]),
+    ("svo_tracking_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i64p]),
+    ("svo_tracking_map_frame", C.c_int, [_vp, C.c_int, _i64p, _f64p, _f32p, _f64p, _i64p, C.c_int, _i32p]),
     ("svo_tracking_trace", C.c_int64, [_vp, C.c_char_p, _vp, C.c_int64]),
 ]
 SYMBOLS = [s[0] for s in _SIGS]
@@ -129,7 +131,42 @@ class Tracking:
             raise SvoError(lib().svo_tracking_last_error(self.handle).decode())
         return rc == 1
 
-    def frame_info(self) -> dict:
+    def bundle_adjust(self, window=5, n_fixed=2, huber_delta=0.0, max_iterations=20) -> dict:
+        """Windowed bundle adjustment of the map (Map::localBundleAdjust): the last
+        `window` frames the map holds (every frame but the newest, which the tracker
+        still owns), the oldest n_fixed of them constant, and the points they see.
+        Opt-in: step() never calls it. -> initial / final cost, iterations, counts."""
+        costs = np.zeros(2, np.float64)
+        it = C.c_int()
+        counts = np.zeros(3, np.int64)
+        rc = lib().svo_tracking_bundle_adjust(self.handle, int(window), int(n_fixed), float(huber_delta),
+                                              int(max_iterations), costs.ctypes.data_as(_f64p), C.byref(it),
+                                              counts.ctypes.data_as(_i64p))
+        if rc < 0:
+            raise SvoError(lib().svo_tracking_last_error(self.handle).decode() or f"bundle_adjust failed ({rc})")
+        return {"initial_cost": costs[0], "final_cost": costs[1], "iterations": it.value, "frames": int(counts[0]),
+                "points": int(counts[1]), "observations": int(counts[2])}
+
+    def _map_frame(self, index):
+        n, fid = C.c_int(), C.c_int64()
+        pose = np.zeros(12, np.float64)
+        nfr = lib().svo_tracking_map_frame(self.handle, int(index), C.byref(fid), pose.ctypes.data_as(_f64p), None,
+                                           None, None, 0, C.byref(n))
+        if nfr < 0:
+            raise SvoError(f"the map holds no frame {index}")
+        k = n.value
+        xy, world, ids = np.zeros((k, 2), np.float32), np.zeros((k, 3), np.float64), np.zeros(k, np.int64)
+        lib().svo_tracking_map_frame(self.handle, int(index), None, None, xy.ctypes.data_as(_f32p),
+                                     world.ctypes.data_as(_f64p), ids.ctypes.data_as(_i64p), k, C.byref(n))
+        info = {"id": fid.value, "features": k, "map_frames": nfr, "R": pose[:9].reshape(3, 3).copy(),
+                "t": pose[9:].copy()}
+        return info, (xy, world, ids)
+
+    def frame_info(self, map_index=None) -> dict:
+        """The frame the last step produced, or with map_index the map's frame of that
+        index (insertion order, negative from the newest): id, pose (camera -> world)."""
+        if map_index is not None:
+            return self._map_frame(map_index)[0]
         fid, kf, nf, nmp = C.c_int64(), C.c_int(), C.c_int64(), C.c_int64()
         ir = C.c_double()
         pose = np.zeros(12, np.float64)
@@ -139,7 +176,11 @@ class Tracking:
         return {"id": fid.value, "keyframe": bool(kf.value), "features": nf.value, "map_points": nmp.value,
                 "inlier_ratio": ir.value, "R": pose[:9].reshape(3, 3).copy(), "t": pose[9:].copy()}
 
-    def features(self):
+    def features(self, map_index=None):
+        """(xy, map point world positions, map point ids) of the last frame's left
+        features, or of the map's frame map_index."""
+        if map_index is not None:
+            return self._map_frame(map_index)[1]
         n = C.c_int()
         lib().svo_tracking_features(self.handle, None, None, None, 0, C.byref(n))
         k = n.value
