@@ -291,6 +291,31 @@ int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points,
  * n_cams + 1): camera j's staged positions, ascending. */
 int svo_ba_sort_observations(const int* obs_cam, const int* obs_point, int n_obs, int n_cams, int n_points,
                              int* order, int* pt_off, int* cam_off, int* cam_idx);
+/* The same staging on the device, from observations that arrive as n_cams lists
+ * per problem, one per camera, each with strictly increasing point ids (the
+ * batched front end's feature lists): ids (P*n_cams*cap), xy (P*n_cams*cap*2),
+ * counts (P*n_cams, 0 .. cap). The (point, camera) order is then a merge of
+ * sorted lists, found by binary searches without a sort or an atomic. Outputs
+ * per problem, strides max_obs = max_points = n_cams*cap, any may be NULL: what
+ * svo_ba_sort_observations gives for the same observations listed camera by
+ * camera with the points numbered by ascending id -- ocam / oxy (the staged
+ * observations' cameras and pixels), pt_off (P*(n_cams*cap + 1), n_obs behind
+ * the last point), cam_off (P*(n_cams + 1)), cam_idx -- plus cam_pt (the point of
+ * the observation cam_idx names), pt_id (each point's id), n_points and n_obs
+ * (P). Zero behind a problem's last observation / point. SVO_ERR_ARG (nothing
+ * written): n_cams outside 1 .. SVO_BA_MAX_CAMS, a count outside 0 .. cap, a
+ * negative id, a list that is not strictly increasing. */
+int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                       const float* xy, int* ocam, float* oxy, int* pt_off, int* cam_off, int* cam_idx, int* cam_pt,
+                       int* pt_id, int* n_points, int* n_obs);
+/* The device staging chain (svo_ba_stage_lists' kernels into a block sized from
+ * the staged counts, as svo_frontend_bundle_adjust runs it) timed with HIP
+ * events: reps runs after one warm-up, ms per chain (ms_device). Beside it what
+ * the host's staging of the same lists costs, wall time: the lists' download
+ * (ms_host_readback) and svo_bundle_adjust's sort and uploads (ms_host_stage). */
+int svo_ba_time_staging(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                        const float* xy, int reps, double* ms_device, double* ms_host_readback,
+                        double* ms_host_stage);
 /* One LM iteration's launch chain (linearise, eliminate, solve, update, trial
  * cost) timed with HIP events: reps runs after one warm-up, ms per iteration. */
 int svo_ba_time_iteration(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
@@ -445,6 +470,42 @@ int svo_frontend_features(svo_frontend* fe, int seq, float* xy, int cap, int* n)
 /* World positions (MapPoint::mWorldPos) of the current features' map points, in
  * feature order (synchronises the front end first). */
 int svo_frontend_map_points(svo_frontend* fe, int seq, double* xyz, int cap, int* n);
+/* The observation window: the back end's input, kept on the device. Each sequence
+ * gets a ring of `window` (1 .. SVO_BA_MAX_CAMS) slots; svo_frontend_init and
+ * every svo_frontend_step record the frame's feature list as the step leaves it
+ * (svo_frontend_features' points with their map ids) in stream order, without a
+ * host wait, and the frame's pose (world -> camera, R row-major and t: 12 doubles,
+ * the solvePnPRansac model [R(rvec) | tvec]; the identity for the init frame and
+ * for a frame without a model) once its final fit lands. A map reclaim (n_frames
+ * above) renumbers a sequence's map ids: the slots recorded before it are no
+ * longer valid, so that sequence's window shortens to the frames since the
+ * reclaim and grows again. Before svo_frontend_init; SVO_ERR_ARG afterwards, or
+ * with `window` out of range. A front end that never calls it runs exactly as
+ * before: no kernel is added to its step. */
+int svo_frontend_window_enable(svo_frontend* fe, int window);
+/* The valid slots of sequence seq, oldest first (synchronises the front end
+ * first): n_frames of them; frame_t (W = the enabled window), poses (W*12),
+ * counts (W), ids (W*cap: map ids, strictly increasing per frame), xy (W*cap*2);
+ * a frame with more than cap features is cut to cap. Any output may be NULL. */
+int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* frame_t, double* poses, int* counts,
+                        int* ids, float* xy);
+/* Windowed bundle adjustment (svo_bundle_adjust's Levenberg-Marquardt, config K)
+ * of every sequence from its own window, without leaving the device: the
+ * observations are staged from the ring (svo_ba_stage_lists' chain), the points
+ * gathered from the map by id, the oldest n_fixed valid frames held constant.
+ * Refined points go back into the map, so the next step's PnP sees them; refined
+ * poses go back into the window (svo_frontend_pose keeps reporting the PnP fit).
+ * Host <-> device traffic: the staged counts, and the control numbers per problem
+ * and iteration that svo_bundle_adjust exchanges. costs: S*2 (initial, final),
+ * iterations: S, sizes: S*3 (frames, points, observations); any may be NULL.
+ * The results equal svo_bundle_adjust's, bit for bit, on the same window given
+ * frame by frame with the points numbered by ascending map id and max_points /
+ * max_obs the batch's largest counts. A sequence with an empty or one-frame window
+ * is a valid problem in which nothing is free: it comes back unchanged.
+ * Synchronises the front end first. SVO_ERR_ARG: window not enabled, n_fixed < 0,
+ * max_iterations < 0. */
+int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations, double* costs,
+                               int* iterations, int* sizes);
 /* Accumulated per-phase device time (ms) and launch counts since create/reset:
  * phases: 0 pyramid (left + Scharr), 1 lk, 2 post_lk, 3 stereo_lk, 4 pnp_score,
  * 5 tail (keyframe), 6 fast, 7 bucket, 8 append, 9 pyramid_right. Returns the number

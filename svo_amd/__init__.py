@@ -132,6 +132,10 @@ _SIGS = [
                                    _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
                                    _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]),
     ("svo_ba_sort_observations", C.c_int, [_i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p]),
+    ("svo_ba_stage_lists", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _i32p, _f32p, _i32p, _i32p,
+                                     _i32p, _i32p, _i32p, _i32p, _i32p]),
+    ("svo_ba_time_staging", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_int, _f64p, _f64p,
+                                      _f64p]),
     ("svo_ba_time_iteration", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p,
                                         _f64p, _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_double, C.c_int, _f64p]),
     ("svo_frontend_create", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -139,6 +143,9 @@ _SIGS = [
     ("svo_frontend_set_frame", C.c_int, [_vp, C.c_int, C.c_int, _u8p, _u8p, C.c_int]),
     ("svo_frontend_set_frame_bgr", C.c_int, [_vp, C.c_int, C.c_int, _u8p, _u8p, C.c_int]),
     ("svo_frontend_map_points", C.c_int, [_vp, C.c_int, _f64p, C.c_int, _i32p]),
+    ("svo_frontend_window_enable", C.c_int, [_vp, C.c_int]),
+    ("svo_frontend_window", C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _f64p, _i32p, _i32p, _f32p]),
+    ("svo_frontend_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
     ("svo_frontend_time_pyramid", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_time_fast", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_pyramid_level", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
@@ -629,6 +636,43 @@ class Context:
         out["n_free"], out["status"] = nfree, status
         return {k: v[0] for k, v in out.items()} if single else out
 
+    def ba_stage_lists(self, counts, ids, xy) -> dict:
+        """The bundle adjustment's staging on the device (svo_ba_stage_lists) of
+        observations given as sorted lists per camera: counts (P, W), ids (P, W, cap)
+        strictly increasing per list, xy (P, W, cap, 2) -> dict of ocam (P, O), oxy
+        (P, O, 2), pt_off (P, O + 1), cam_off (P, W + 1), cam_idx, cam_pt, pt_id
+        (P, O), n_points, n_obs (P,), O = W * cap."""
+        counts = _c(counts, np.int32)
+        P, W = counts.shape
+        ids = _c(ids, np.int32).reshape(P, W, -1)
+        cap = ids.shape[2]
+        xy = _c(xy, np.float32).reshape(P, W, cap, 2)
+        O = W * cap
+        out = {"ocam": np.zeros((P, O), np.int32), "oxy": np.zeros((P, O, 2), np.float32),
+               "pt_off": np.zeros((P, O + 1), np.int32), "cam_off": np.zeros((P, W + 1), np.int32),
+               "cam_idx": np.zeros((P, O), np.int32), "cam_pt": np.zeros((P, O), np.int32),
+               "pt_id": np.zeros((P, O), np.int32), "n_points": np.zeros(P, np.int32), "n_obs": np.zeros(P, np.int32)}
+        self._check(lib().svo_ba_stage_lists(
+            self.handle, P, W, cap, _p(counts, _i32p), _p(ids, _i32p), _p(xy, _f32p), _p(out["ocam"], _i32p),
+            _p(out["oxy"], _f32p), *[_p(out[k], _i32p) for k in ("pt_off", "cam_off", "cam_idx", "cam_pt", "pt_id",
+                                                                  "n_points", "n_obs")]))
+        return out
+
+    def ba_time_staging(self, counts, ids, xy, reps: int = 20) -> dict:
+        """ms of the device staging chain (HIP events) and, wall time, of the host's
+        way for the same lists: their download and svo_bundle_adjust's sort + uploads
+        (svo_ba_time_staging)."""
+        counts = _c(counts, np.int32)
+        P, W = counts.shape
+        ids = _c(ids, np.int32).reshape(P, W, -1)
+        cap = ids.shape[2]
+        xy = _c(xy, np.float32).reshape(P, W, cap, 2)
+        ms = np.zeros(3)
+        self._check(lib().svo_ba_time_staging(self.handle, P, W, cap, _p(counts, _i32p), _p(ids, _i32p),
+                                              _p(xy, _f32p), int(reps), _p(ms[0:], _f64p), _p(ms[1:], _f64p),
+                                              _p(ms[2:], _f64p)))
+        return {"ms_device": float(ms[0]), "ms_host_readback": float(ms[1]), "ms_host_stage": float(ms[2])}
+
     def ba_time_iteration(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, lam: float = 1e-4,
                           n_cams=None, n_points=None, n_obs=None, huber_delta: float = 0.0, reps: int = 10) -> float:
         """ms per LM iteration of the bundle adjustment's launch chain (HIP events)."""
@@ -820,6 +864,43 @@ class Frontend:
         n = C.c_int()
         self.ctx._check(lib().svo_frontend_map_points(self.handle, seq, _p(xyz, _f64p), cap, C.byref(n)))
         return xyz[: min(n.value, cap)].copy()
+
+    def window_enable(self, window):
+        """Keep the last `window` (1 .. BA_MAX_CAMS) frames' observations per sequence
+        on the device (svo_frontend_window_enable); once, before init."""
+        self.ctx._check(lib().svo_frontend_window_enable(self.handle, int(window)))
+        self._window = int(window)
+
+    def window(self, seq):
+        """The valid frames of sequence seq's window, oldest first (svo_frontend_window)
+        -> dict of frame_t (n,), poses (n, 12) world -> camera, ids and xy: lists of n
+        arrays (k,) int32 map ids / (k, 2) float32 pixels."""
+        W = getattr(self, "_window", 0) or 1
+        cap = (self.cfg.n_features + 63) // 64 * 64
+        n = C.c_int()
+        ft, cnt = np.zeros(W, np.int32), np.zeros(W, np.int32)
+        poses = np.zeros((W, 12), np.float64)
+        ids = np.zeros((W, cap), np.int32)
+        xy = np.zeros((W, cap, 2), np.float32)
+        self.ctx._check(lib().svo_frontend_window(self.handle, int(seq), cap, C.byref(n), _p(ft, _i32p),
+                                                  _p(poses, _f64p), _p(cnt, _i32p), _p(ids, _i32p), _p(xy, _f32p)))
+        k = n.value
+        return {"frame_t": ft[:k].copy(), "poses": poses[:k].copy(),
+                "ids": [ids[j, :cnt[j]].copy() for j in range(k)], "xy": [xy[j, :cnt[j]].copy() for j in range(k)]}
+
+    def bundle_adjust(self, n_fixed=2, huber_delta=0.0, max_iterations=10):
+        """Windowed bundle adjustment of every sequence from its own window, on the
+        device (svo_frontend_bundle_adjust): refined points into the map, refined
+        poses into the window -> (costs (S, 2): initial and final, iterations (S,),
+        sizes (S, 3): frames, points, observations)."""
+        S = self.cfg.n_seq
+        costs = np.zeros((S, 2), np.float64)
+        its = np.zeros(S, np.int32)
+        sizes = np.zeros((S, 3), np.int32)
+        self.ctx._check(lib().svo_frontend_bundle_adjust(self.handle, int(n_fixed), float(huber_delta),
+                                                         int(max_iterations), _p(costs, _f64p), _p(its, _i32p),
+                                                         _p(sizes, _i32p)))
+        return costs, its, sizes
 
     def time_pyramid(self, t, reps=20):
         """ms per pyramid + Scharr launch chain of frame t, timed alone."""

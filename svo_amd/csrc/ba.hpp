@@ -59,4 +59,71 @@ hipError_t launch_ba_cost(const BaBatch& b, const double* poses, const double* p
 hipError_t launch_ba_commit(const BaBatch& b, const int* accept, const double* trial_poses,
                             const double* trial_points, double* poses, double* points, hipStream_t st);
 
+// ---- device staging (ba_stage.hip): a problem's observations arrive as W lists
+// on the device, one per camera, each with strictly increasing point ids (the
+// front end's feature lists), so the (point, camera) order
+// above is a merge of W sorted lists and every staged position follows from
+// binary searches alone: no sort, no atomics, a fixed order.
+// Camera j of problem p reads list l = slot ? slot[p W + j] : j of the
+// problem's W lists: counts[p W + j] entries of ids / xy at (p W + l) cap.
+struct BaLists {
+    int P, W, cap;
+    const int* slot;    // [P][W], nullable
+    const int* counts;  // [P][W], by camera
+    const int* ids;     // [P][W][cap], by list
+    const float* xy;    // [P][W][cap][2], by list
+};
+// the chain's own memory, sized for W cap observations per problem (12 bytes each)
+struct BaStageWork {
+    int* pos;       // [P][W cap]: staged position | first-of-its-point << 31, by (camera, k)
+    int* part;      // [P][ba_stage_blocks]: first observations per placing workgroup
+    int* flag;      // [P][W cap]: by staged position, first-of-its-point, then the point index
+    int* smid;      // [P][W cap]: by staged position, the point's id
+    int* n_points;  // [P]
+    int* n_obs;     // [P]
+};
+// the BA's arrays the chain fills, strides maxM / maxO / W (BaBatch's layout);
+// points, map, n_cams_out are nullable (map: [P][map_cap][3], gathered by id)
+struct BaStageOut {
+    int maxM, maxO;
+    int *ocam, *pt_off, *cam_off, *cam_idx, *cam_pt, *pt_id, *n_points;
+    float* oxy;
+    double* points;
+    const double* map;
+    int map_cap;
+};
+int ba_stage_blocks(int W, int cap);
+size_t ba_stage_work_bytes(int P, int W, int cap);
+BaStageWork ba_stage_carve(void* mem, int P, int W, int cap);
+// pass 1: every observation's staged position and the counts n_points / n_obs
+hipError_t launch_ba_stage_place(const BaLists& l, const BaStageWork& w, hipStream_t st);
+// pass 2: the observations into (point, camera) order, the index lists per point
+// and per camera, the compact points and their ids
+hipError_t launch_ba_stage_fill(const BaLists& l, const BaStageWork& w, const BaStageOut& o, hipStream_t st);
+// The cameras of a window: poses[p][j] = ring[(p W + slot[p W + j]) 12 ..] for j <
+// n_cams[p] (zero behind), fixed[p][j] = j < n_fixed or j >= n_cams[p].
+hipError_t launch_ba_stage_cams(const BaLists& l, const int* n_cams, const double* ring, int n_fixed, double* poses,
+                                uint8_t* fixed, hipStream_t st);
+// Back from the BA: points[p][i] to map[p][pt_id[i]] for i < n_points[p], the free
+// cameras' poses to their ring slots.
+hipError_t launch_ba_stage_unstage(const BaLists& l, const int* n_cams, const int* n_points, const int* pt_id,
+                                   int maxM, const double* points, const double* poses, const uint8_t* fixed,
+                                   double* map, int map_cap, double* ring, hipStream_t st);
+
+// A windowed bundle adjustment whose problems lie on the device (bundle.cpp):
+// stage from the lists, run svo_bundle_adjust's LM, write points and poses back.
+// Host <-> device traffic: the staged counts once, the LM's control numbers per
+// iteration. costs [P][2], iterations [P], sizes [P][3] (cameras, points,
+// observations): nullable, host.
+struct BaDeviceWindow {
+    BaLists lists;
+    const int* n_cams;  // [P] device: valid cameras (the first of each problem's W)
+    double* ring;       // poses by list: [(p W + l) 12], world -> camera
+    double* map;        // [P][map_cap][3]
+    int map_cap;
+    int n_fixed;
+};
+int ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[9], double huber_delta,
+                     int max_iterations, double* costs, int* iterations, int* sizes);
+
 }  // namespace svo

@@ -3,7 +3,11 @@
 // and per camera) and the Levenberg-Marquardt control over the device stages of
 // ba.hip. Poses, points and observations go up once and come down once; per
 // iteration the host reads a cost, a status flag and the step size per problem
-// and sends back lambda and the accept / active flags.
+// and sends back lambda and the accept / active flags. A problem batch that
+// already lies on the device as sorted lists per camera (the front end's window)
+// is staged there instead (ba_stage.hip, ba_adjust_device) and runs the same LM.
+#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -73,8 +77,103 @@ struct Staged {
     double *poses, *points, *tposes, *tpoints, *cost, *tcost, *S, *bvec, *dp, *lambda;
     int *active, *accept;
     int nblk;
+    // the staged problem (what b's const pointers name), for whoever fills it
+    int *n_cams, *n_points, *ocam, *cam_idx, *cam_pt, *pt_off, *cam_off, *pt_id;
+    float* oxy;
+    uint8_t* fixed;
 };
 
+struct Sizes {
+    int P, maxC, maxM, maxO;
+};
+
+// The device block of a batch of that size, carved: everything the LM's stages
+// read and write. Nothing is filled (S / bvec are zeroed); want_ids: pt_id
+// [P][maxM], the device staging's map ids.
+int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bool want_S, bool want_dp,
+                 bool want_ids, Staged& s) {
+    const size_t P = (size_t)a.P, nC = P * a.maxC, nM = P * a.maxM, nO = P * a.maxO;
+    s.nblk = ba_point_blocks(a.maxM);
+    const size_t ld = 6 * (size_t)a.maxC;
+    const size_t dbl = 2 * 12 * nC + 2 * 3 * nM + kBaNE * nC + 6 * nM + 3 * nM + 6 * nM + 6 * nC +
+                       2 * P * s.nblk + 2 * P + nC + 3 * P + (want_S ? P * ld * ld + P * ld : 0) +
+                       (want_dp ? 3 * nM : 0);
+    const size_t ints = 2 * P + 3 * nO + P * (a.maxM + 1) + P * (a.maxC + 1) + nC + nM + 4 * P + (want_ids ? nM : 0);
+    const size_t bytes = sizeof(double) * dbl + sizeof(int) * ints + sizeof(float) * 2 * nO + nC + 64 * 256;
+    char* d = (char*)scratch(ctx, 11, bytes);
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    auto carve = [&](size_t n) {
+        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
+        char* r = d;
+        d += n;
+        return r;
+    };
+    auto dd = [&](size_t n) { return (double*)carve(sizeof(double) * n); };
+    auto di = [&](size_t n) { return (int*)carve(sizeof(int) * n); };
+    BaBatch& b = s.b;
+    b.P = a.P;
+    b.maxC = a.maxC;
+    b.maxM = a.maxM;
+    b.maxO = a.maxO;
+    b.fx = K[0];
+    b.fy = K[4];
+    b.cx = K[2];
+    b.cy = K[5];
+    b.delta = delta;
+    s.poses = dd(12 * nC);
+    s.tposes = dd(12 * nC);
+    s.points = dd(3 * nM);
+    s.tpoints = dd(3 * nM);
+    b.cam_ne = dd(kBaNE * nC);
+    b.pt_V = dd(6 * nM);
+    b.pt_g = dd(3 * nM);
+    b.pt_Vinv = dd(6 * nM);
+    b.dc = dd(6 * nC);
+    b.step_part = dd(2 * P * s.nblk);
+    b.stepinfo = dd(2 * P);
+    b.cam_cost = dd(nC);
+    s.cost = dd(P);
+    s.tcost = dd(P);
+    s.lambda = dd(P);
+    s.S = want_S ? dd(P * ld * ld) : nullptr;
+    s.bvec = want_S ? dd(P * ld) : nullptr;
+    s.dp = want_dp ? dd(3 * nM) : nullptr;
+    s.n_cams = di(P);
+    s.n_points = di(P);
+    s.ocam = di(nO);
+    s.cam_idx = di(nO);
+    s.cam_pt = di(nO);
+    s.pt_off = di(P * (a.maxM + 1));
+    s.cam_off = di(P * (a.maxC + 1));
+    b.cam_cnt = di(nC);
+    b.pt_free = di(nM);
+    b.status = di(P);
+    b.n_free = di(P);
+    s.active = di(P);
+    s.accept = di(P);
+    s.pt_id = want_ids ? di(nM) : nullptr;
+    s.oxy = (float*)carve(sizeof(float) * 2 * nO);
+    s.fixed = (uint8_t*)carve(nC);
+    b.n_cams = s.n_cams;
+    b.n_points = s.n_points;
+    b.ocam = s.ocam;
+    b.cam_idx = s.cam_idx;
+    b.cam_pt = s.cam_pt;
+    b.pt_off = s.pt_off;
+    b.cam_off = s.cam_off;
+    b.oxy = s.oxy;
+    b.fixed = s.fixed;
+    b.lambda = s.lambda;
+    b.active = s.active;
+    if (s.S) {
+        SVO_HIP(ctx, hipMemsetAsync(s.S, 0, sizeof(double) * P * ld * ld, ctx->stream));
+        SVO_HIP(ctx, hipMemsetAsync(s.bvec, 0, sizeof(double) * P * ld, ctx->stream));
+    }
+    return SVO_OK;
+}
+
+// The host's problem into the block: the stable sort by (point, camera) and the
+// uploads.
 int stage(svo_ctx* ctx, const Args& a, bool want_S, bool want_dp, Staged& s) {
     const size_t P = (size_t)a.P, nC = P * a.maxC, nM = P * a.maxM, nO = P * a.maxO;
     std::vector<int> h_nc(P), h_nm(P), ocam(nO, 0), pt_off(P * (a.maxM + 1), 0), cam_off(P * (a.maxC + 1), 0),
@@ -100,96 +199,23 @@ int stage(svo_ctx* ctx, const Args& a, bool want_S, bool want_dp, Staged& s) {
         }
         for (int k = 0; k < O; k++) cam_pt[p * a.maxO + k] = pt[order[cam_idx[p * a.maxO + k]]];
     }
-    s.nblk = ba_point_blocks(a.maxM);
-    const size_t ld = 6 * (size_t)a.maxC;
-    const size_t dbl = 2 * 12 * nC + 2 * 3 * nM + kBaNE * nC + 6 * nM + 3 * nM + 6 * nM + 6 * nC +
-                       2 * P * s.nblk + 2 * P + nC + 3 * P + (want_S ? P * ld * ld + P * ld : 0) +
-                       (want_dp ? 3 * nM : 0);
-    const size_t ints = 2 * P + 3 * nO + P * (a.maxM + 1) + P * (a.maxC + 1) + nC + nM + 4 * P;
-    const size_t bytes = sizeof(double) * dbl + sizeof(int) * ints + sizeof(float) * 2 * nO + nC + 64 * 256;
-    char* d = (char*)scratch(ctx, 11, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    auto carve = [&](size_t n) {
-        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
-        char* r = d;
-        d += n;
-        return r;
-    };
-    auto dd = [&](size_t n) { return (double*)carve(sizeof(double) * n); };
-    auto di = [&](size_t n) { return (int*)carve(sizeof(int) * n); };
-    BaBatch& b = s.b;
-    b.P = a.P;
-    b.maxC = a.maxC;
-    b.maxM = a.maxM;
-    b.maxO = a.maxO;
-    b.fx = a.K[0];
-    b.fy = a.K[4];
-    b.cx = a.K[2];
-    b.cy = a.K[5];
-    b.delta = a.delta;
-    s.poses = dd(12 * nC);
-    s.tposes = dd(12 * nC);
-    s.points = dd(3 * nM);
-    s.tpoints = dd(3 * nM);
-    b.cam_ne = dd(kBaNE * nC);
-    b.pt_V = dd(6 * nM);
-    b.pt_g = dd(3 * nM);
-    b.pt_Vinv = dd(6 * nM);
-    b.dc = dd(6 * nC);
-    b.step_part = dd(2 * P * s.nblk);
-    b.stepinfo = dd(2 * P);
-    b.cam_cost = dd(nC);
-    s.cost = dd(P);
-    s.tcost = dd(P);
-    s.lambda = dd(P);
-    s.S = want_S ? dd(P * ld * ld) : nullptr;
-    s.bvec = want_S ? dd(P * ld) : nullptr;
-    s.dp = want_dp ? dd(3 * nM) : nullptr;
-    int* d_nc = di(P);
-    int* d_nm = di(P);
-    int* d_ocam = di(nO);
-    int* d_cam_idx = di(nO);
-    int* d_cam_pt = di(nO);
-    int* d_pt_off = di(P * (a.maxM + 1));
-    int* d_cam_off = di(P * (a.maxC + 1));
-    b.cam_cnt = di(nC);
-    b.pt_free = di(nM);
-    b.status = di(P);
-    b.n_free = di(P);
-    s.active = di(P);
-    s.accept = di(P);
-    float* d_oxy = (float*)carve(sizeof(float) * 2 * nO);
-    uint8_t* d_fixed = (uint8_t*)carve(nC);
-    b.n_cams = d_nc;
-    b.n_points = d_nm;
-    b.ocam = d_ocam;
-    b.cam_idx = d_cam_idx;
-    b.cam_pt = d_cam_pt;
-    b.pt_off = d_pt_off;
-    b.cam_off = d_cam_off;
-    b.oxy = d_oxy;
-    b.fixed = d_fixed;
-    b.lambda = s.lambda;
-    b.active = s.active;
+    int rc = alloc_staged(ctx, Sizes{a.P, a.maxC, a.maxM, a.maxO}, a.K, a.delta, want_S, want_dp, false, s);
+    if (rc) return rc;
     hipStream_t st = ctx->stream;
     auto up = [&](void* dst, const void* src, size_t n) {
         return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st) : hipSuccess;
     };
     SVO_HIP(ctx, up(s.poses, a.poses, sizeof(double) * 12 * nC));
     SVO_HIP(ctx, up(s.points, a.points, sizeof(double) * 3 * nM));
-    SVO_HIP(ctx, up(d_fixed, a.fixed, nC));
-    SVO_HIP(ctx, up(d_nc, h_nc.data(), sizeof(int) * P));
-    SVO_HIP(ctx, up(d_nm, h_nm.data(), sizeof(int) * P));
-    SVO_HIP(ctx, up(d_ocam, ocam.data(), sizeof(int) * nO));
-    SVO_HIP(ctx, up(d_cam_idx, cam_idx.data(), sizeof(int) * nO));
-    SVO_HIP(ctx, up(d_cam_pt, cam_pt.data(), sizeof(int) * nO));
-    SVO_HIP(ctx, up(d_pt_off, pt_off.data(), sizeof(int) * pt_off.size()));
-    SVO_HIP(ctx, up(d_cam_off, cam_off.data(), sizeof(int) * cam_off.size()));
-    SVO_HIP(ctx, up(d_oxy, oxy.data(), sizeof(float) * 2 * nO));
-    if (s.S) {
-        SVO_HIP(ctx, hipMemsetAsync(s.S, 0, sizeof(double) * P * ld * ld, st));
-        SVO_HIP(ctx, hipMemsetAsync(s.bvec, 0, sizeof(double) * P * ld, st));
-    }
+    SVO_HIP(ctx, up(s.fixed, a.fixed, nC));
+    SVO_HIP(ctx, up(s.n_cams, h_nc.data(), sizeof(int) * P));
+    SVO_HIP(ctx, up(s.n_points, h_nm.data(), sizeof(int) * P));
+    SVO_HIP(ctx, up(s.ocam, ocam.data(), sizeof(int) * nO));
+    SVO_HIP(ctx, up(s.cam_idx, cam_idx.data(), sizeof(int) * nO));
+    SVO_HIP(ctx, up(s.cam_pt, cam_pt.data(), sizeof(int) * nO));
+    SVO_HIP(ctx, up(s.pt_off, pt_off.data(), sizeof(int) * pt_off.size()));
+    SVO_HIP(ctx, up(s.cam_off, cam_off.data(), sizeof(int) * cam_off.size()));
+    SVO_HIP(ctx, up(s.oxy, oxy.data(), sizeof(float) * 2 * nO));
     // the staging vectors go out of scope on return: the copies must have left them
     SVO_HIP(ctx, hipStreamSynchronize(st));
     return SVO_OK;
@@ -215,9 +241,341 @@ int launch_solve_chain(svo_ctx* ctx, Staged& s) {
     return SVO_OK;
 }
 
+// svo_bundle_adjust's Levenberg-Marquardt control over a filled block: the
+// refined state stays in s.poses / s.points. c_first / c_cur: the initial and the
+// final cost, its: the iterations each problem took.
+int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, std::vector<double>& c_first, std::vector<double>& c_cur,
+           std::vector<int>& its) {
+    const size_t P = (size_t)s.b.P;
+    int rc;
+    hipStream_t st = ctx->stream;
+    std::vector<double> lambda(P, 1e-4), c_trial(P), stepinfo(2 * P);
+    std::vector<int> active(P, 1), accept(P), status(P), done(P, 0);
+    c_cur.assign(P, 0.0);
+    its.assign(P, 0);
+    auto read_back = [&]() -> int {
+        SVO_HIP(ctx, hipMemcpyAsync(c_trial.data(), s.tcost, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipMemcpyAsync(stepinfo.data(), s.b.stepinfo, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipMemcpyAsync(status.data(), s.b.status, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipStreamSynchronize(st));
+        return SVO_OK;
+    };
+    if ((rc = send_control(ctx, s, lambda, active))) return rc;
+    SVO_HIP(ctx, launch_ba_cost(s.b, s.poses, s.points, s.cost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(c_cur.data(), s.cost, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    c_first = c_cur;
+    for (int it = 0; it < max_iterations; it++) {
+        bool any = false;
+        for (size_t p = 0; p < P; p++) {
+            active[p] = !done[p];
+            any = any || active[p];
+        }
+        if (!any) break;
+        if ((rc = send_control(ctx, s, lambda, active))) return rc;
+        SVO_HIP(ctx, launch_ba_linearize(s.b, s.poses, s.points, st));
+        if ((rc = launch_solve_chain(ctx, s))) return rc;
+        if ((rc = read_back())) return rc;
+        // reduced system not positive definite: raise lambda and solve again from
+        // the same linearisation, as lm_solve's caller does
+        for (;;) {
+            bool retry = false;
+            for (size_t p = 0; p < P; p++) {
+                const bool again = active[p] && status[p] != 0;
+                if (again) {
+                    lambda[p] *= 10;
+                    if (lambda[p] >= 1e16) {
+                        done[p] = 1;
+                        active[p] = 0;
+                        continue;
+                    }
+                    retry = true;
+                } else if (active[p] && status[p] == 0) {
+                    active[p] = 2;  // solved: waits for the verdict below
+                }
+            }
+            if (!retry) break;
+            std::vector<int> again(P);
+            for (size_t p = 0; p < P; p++) again[p] = active[p] == 1;
+            if ((rc = send_control(ctx, s, lambda, again))) return rc;
+            // V*^-1 depends on lambda, so stage 1 runs again (its camera pass repeats itself)
+            SVO_HIP(ctx, launch_ba_linearize(s.b, s.poses, s.points, st));
+            if ((rc = launch_solve_chain(ctx, s))) return rc;
+            if ((rc = read_back())) return rc;
+        }
+        for (size_t p = 0; p < P; p++) {
+            accept[p] = 0;
+            if (done[p]) continue;
+            its[p]++;
+            if (active[p] != 2) continue;
+            if (std::sqrt(stepinfo[2 * p]) < 1e-12 * (1 + std::sqrt(stepinfo[2 * p + 1]))) {
+                done[p] = 1;
+                continue;
+            }
+            const double c0 = c_cur[p], c1 = c_trial[p];
+            if (c1 <= c0) {
+                accept[p] = 1;
+                c_cur[p] = c1;
+                lambda[p] = lambda[p] * 0.1 > 1e-12 ? lambda[p] * 0.1 : 1e-12;
+                if (c0 - c1 <= 1e-15 * c0) done[p] = 1;
+            } else {
+                lambda[p] *= 10;
+                if (lambda[p] >= 1e16) done[p] = 1;
+            }
+        }
+        SVO_HIP(ctx, hipMemcpyAsync(s.accept, accept.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, launch_ba_commit(s.b, s.accept, s.tposes, s.tpoints, s.poses, s.points, st));
+        SVO_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return SVO_OK;
+}
+
+// The staging chain's own memory (scratch slot 12: the LM's block lives in 11).
+int stage_work(svo_ctx* ctx, const BaLists& l, BaStageWork& w) {
+    void* d = scratch(ctx, 12, ba_stage_work_bytes(l.P, l.W, l.cap));
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    w = ba_stage_carve(d, l.P, l.W, l.cap);
+    return SVO_OK;
+}
+
+// Host lists, checked (null when they are fine) ...
+const char* check_lists(int P, int W, int cap, const int* counts, const int* ids, const float* xy) {
+    if (P < 0 || W < 1 || W > SVO_BA_MAX_CAMS || cap < 1 || (int64_t)W * cap > (1 << 24)) return "sizes";
+    if (P == 0) return nullptr;
+    if (!counts || !ids || !xy) return "lists are null";
+    for (size_t q = 0; q < (size_t)P * W; q++) {
+        if (counts[q] < 0 || counts[q] > cap) return "count outside 0 .. cap";
+        const int* a = ids + q * cap;
+        for (int k = 0; k < counts[q]; k++)
+            if (a[k] < 0 || (k > 0 && a[k] <= a[k - 1])) return "ids not strictly increasing";
+    }
+    return nullptr;
+}
+
+// ... and uploaded as they are (scratch slot 9)
+int upload_lists(svo_ctx* ctx, int P, int W, int cap, const int* counts, const int* ids, const float* xy, BaLists& l) {
+    const size_t nL = (size_t)P * W, nO = nL * cap;
+    char* in = (char*)scratch(ctx, 9, sizeof(int) * (nL + nO) + sizeof(float) * 2 * nO + 1024);
+    if (!in) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    int* d_counts = (int*)in;
+    int* d_ids = (int*)(in + ((sizeof(int) * nL + 255) & ~(size_t)255));
+    float* d_xy = (float*)((char*)d_ids + ((sizeof(int) * nO + 255) & ~(size_t)255));
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(d_counts, counts, sizeof(int) * nL, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(d_ids, ids, sizeof(int) * nO, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * nO, hipMemcpyHostToDevice, st));
+    l = BaLists{P, W, cap, nullptr, d_counts, d_ids, d_xy};
+    return SVO_OK;
+}
+
+// what the host's stage() leaves zero behind a problem's last observation
+int zero_observations(svo_ctx* ctx, const Staged& s) {
+    const size_t nO = (size_t)s.b.P * s.b.maxO;
+    for (int* a : {s.ocam, s.cam_idx, s.cam_pt}) SVO_HIP(ctx, hipMemsetAsync(a, 0, sizeof(int) * nO, ctx->stream));
+    SVO_HIP(ctx, hipMemsetAsync(s.oxy, 0, sizeof(float) * 2 * nO, ctx->stream));
+    return SVO_OK;
+}
+
+BaStageOut stage_out(const Staged& s, const double* map, int map_cap) {
+    BaStageOut o;
+    o.maxM = s.b.maxM;
+    o.maxO = s.b.maxO;
+    o.ocam = s.ocam;
+    o.pt_off = s.pt_off;
+    o.cam_off = s.cam_off;
+    o.cam_idx = s.cam_idx;
+    o.cam_pt = s.cam_pt;
+    o.pt_id = s.pt_id;
+    o.n_points = s.n_points;
+    o.oxy = s.oxy;
+    o.points = map ? s.points : nullptr;
+    o.map = map;
+    o.map_cap = map_cap;
+    return o;
+}
+
 }  // namespace
 
+// The LM's block is sized from the staged counts (the largest problem's points
+// and observations, one download of 3 P ints behind the placing pass), not from
+// the worst case W cap: at ~200 bytes per point the block of 256 windows of 8 x
+// 2000 features (~2070 points each, not 16384) is several times smaller. The
+// staging's own 12 bytes per possible observation are sized for the worst case.
+int svo::ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[9], double huber_delta,
+                          int max_iterations, double* costs, int* iterations, int* sizes) {
+    const BaLists& l = w.lists;
+    const size_t P = (size_t)l.P;
+    hipStream_t st = ctx->stream;
+    BaStageWork wk;
+    int rc = stage_work(ctx, l, wk);
+    if (rc) return rc;
+    SVO_HIP(ctx, launch_ba_stage_place(l, wk, st));
+    std::vector<int> h_nc(P), h_nm(P), h_no(P);
+    SVO_HIP(ctx, hipMemcpyAsync(h_nc.data(), w.n_cams, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(h_nm.data(), wk.n_points, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(h_no.data(), wk.n_obs, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    int maxM = 1, maxO = 1;  // (an all-empty batch keeps non-empty arrays)
+    for (size_t p = 0; p < P; p++) {
+        if (h_nm[p] < 0 || h_no[p] < 0 || h_nm[p] > h_no[p] || h_no[p] > l.W * l.cap)
+            return set_error(ctx, SVO_ERR_HIP, "bundle adjustment staging: counts out of range");
+        maxM = std::max(maxM, h_nm[p]);
+        maxO = std::max(maxO, h_no[p]);
+    }
+    Staged s;
+    if ((rc = alloc_staged(ctx, Sizes{l.P, l.W, maxM, maxO}, K, huber_delta, false, false, true, s))) return rc;
+    if ((rc = zero_observations(ctx, s))) return rc;
+    SVO_HIP(ctx, hipMemcpyAsync(s.n_cams, w.n_cams, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    SVO_HIP(ctx, launch_ba_stage_fill(l, wk, stage_out(s, w.map, w.map_cap), st));
+    SVO_HIP(ctx, launch_ba_stage_cams(l, w.n_cams, w.ring, w.n_fixed, s.poses, s.fixed, st));
+    std::vector<double> c_first, c_cur;
+    std::vector<int> its;
+    if ((rc = run_lm(ctx, s, max_iterations, c_first, c_cur, its))) return rc;
+    SVO_HIP(ctx, launch_ba_stage_unstage(l, w.n_cams, s.n_points, s.pt_id, maxM, s.points, s.poses, s.fixed, w.map,
+                                         w.map_cap, w.ring, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t p = 0; p < P; p++) {
+        if (costs) {
+            costs[2 * p] = c_first[p];
+            costs[2 * p + 1] = c_cur[p];
+        }
+        if (iterations) iterations[p] = its[p];
+        if (sizes) {
+            sizes[3 * p] = h_nc[p];
+            sizes[3 * p + 1] = h_nm[p];
+            sizes[3 * p + 2] = h_no[p];
+        }
+    }
+    return SVO_OK;
+}
+
 extern "C" {
+
+int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                       const float* xy, int* ocam, float* oxy, int* pt_off, int* cam_off, int* cam_idx, int* cam_pt,
+                       int* pt_id, int* n_points, int* n_obs) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (const char* why = check_lists(n_problems, n_cams, cap, counts, ids, xy))
+        return set_error(ctx, SVO_ERR_ARG, "svo_ba_stage_lists: %s", why);
+    if (n_problems == 0) return SVO_OK;
+    const size_t P = (size_t)n_problems, WC = (size_t)n_cams * cap, nO = P * WC;
+    // the outputs are a block of the BA's own layout with max_points = max_obs = n_cams * cap
+    hipStream_t st = ctx->stream;
+    BaLists l;
+    BaStageWork wk;
+    int rc = upload_lists(ctx, n_problems, n_cams, cap, counts, ids, xy, l);
+    if (rc || (rc = stage_work(ctx, l, wk))) return rc;
+    const double K[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    Staged s;
+    if ((rc = alloc_staged(ctx, Sizes{n_problems, n_cams, (int)WC, (int)WC}, K, 0.0, false, false, true, s))) return rc;
+    if ((rc = zero_observations(ctx, s))) return rc;
+    SVO_HIP(ctx, hipMemsetAsync(s.pt_id, 0, sizeof(int) * nO, st));
+    SVO_HIP(ctx, launch_ba_stage_place(l, wk, st));
+    SVO_HIP(ctx, launch_ba_stage_fill(l, wk, stage_out(s, nullptr, 0), st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    auto down = [&](void* dst, const void* src, size_t n) {
+        return dst && n ? hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    SVO_HIP(ctx, down(ocam, s.ocam, sizeof(int) * nO));
+    SVO_HIP(ctx, down(oxy, s.oxy, sizeof(float) * 2 * nO));
+    SVO_HIP(ctx, down(pt_off, s.pt_off, sizeof(int) * P * (WC + 1)));
+    SVO_HIP(ctx, down(cam_off, s.cam_off, sizeof(int) * P * (n_cams + 1)));
+    SVO_HIP(ctx, down(cam_idx, s.cam_idx, sizeof(int) * nO));
+    SVO_HIP(ctx, down(cam_pt, s.cam_pt, sizeof(int) * nO));
+    SVO_HIP(ctx, down(pt_id, s.pt_id, sizeof(int) * nO));
+    SVO_HIP(ctx, down(n_points, s.n_points, sizeof(int) * P));
+    SVO_HIP(ctx, down(n_obs, wk.n_obs, sizeof(int) * P));
+    return SVO_OK;
+}
+
+int svo_ba_time_staging(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                        const float* xy, int reps, double* ms_device, double* ms_host_readback,
+                        double* ms_host_stage) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (n_problems < 1 || reps < 1 || !ms_device || !ms_host_readback || !ms_host_stage)
+        return set_error(ctx, SVO_ERR_ARG, "svo_ba_time_staging: bad arguments");
+    if (const char* why = check_lists(n_problems, n_cams, cap, counts, ids, xy))
+        return set_error(ctx, SVO_ERR_ARG, "svo_ba_time_staging: %s", why);
+    const size_t P = (size_t)n_problems, nL = P * n_cams, nO = nL * cap;
+    hipStream_t st = ctx->stream;
+    BaLists l;
+    BaStageWork wk;
+    int rc = upload_lists(ctx, n_problems, n_cams, cap, counts, ids, xy, l);
+    if (rc || (rc = stage_work(ctx, l, wk))) return rc;
+    // the counts size the block, as in ba_adjust_device
+    SVO_HIP(ctx, launch_ba_stage_place(l, wk, st));
+    std::vector<int> h_nm(P), h_no(P);
+    SVO_HIP(ctx, hipMemcpyAsync(h_nm.data(), wk.n_points, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(h_no.data(), wk.n_obs, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    const int maxM = std::max(1, *std::max_element(h_nm.begin(), h_nm.end()));
+    const int maxO = std::max(1, *std::max_element(h_no.begin(), h_no.end()));
+    const double K[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    Staged s;
+    if ((rc = alloc_staged(ctx, Sizes{n_problems, n_cams, maxM, maxO}, K, 0.0, false, false, true, s))) return rc;
+    hipEvent_t e0, e1;
+    SVO_HIP(ctx, hipEventCreate(&e0));
+    SVO_HIP(ctx, hipEventCreate(&e1));
+    rc = SVO_OK;
+    for (int r = -1; r < reps && rc == SVO_OK; r++) {  // r = -1: warm-up
+        if (r == 0 && hipEventRecord(e0, st) != hipSuccess) rc = set_error(ctx, SVO_ERR_HIP, "hipEventRecord");
+        if (rc == SVO_OK && launch_ba_stage_place(l, wk, st) != hipSuccess)
+            rc = set_error(ctx, SVO_ERR_HIP, "launch_ba_stage_place");
+        if (rc == SVO_OK) rc = zero_observations(ctx, s);
+        if (rc == SVO_OK && launch_ba_stage_fill(l, wk, stage_out(s, nullptr, 0), st) != hipSuccess)
+            rc = set_error(ctx, SVO_ERR_HIP, "launch_ba_stage_fill");
+    }
+    float ms = 0;
+    if (rc == SVO_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(ctx, SVO_ERR_HIP, "svo_ba_time_staging: events");
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    *ms_device = (double)ms / reps;
+    // the host's way: the lists come down ...
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    {
+        std::vector<int> b_counts(nL), b_ids(nO);
+        std::vector<float> b_xy(2 * nO);
+        const auto t0 = clk::now();
+        SVO_HIP(ctx, hipMemcpyAsync(b_counts.data(), l.counts, sizeof(int) * nL, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipMemcpyAsync(b_ids.data(), l.ids, sizeof(int) * nO, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipMemcpyAsync(b_xy.data(), l.xy, sizeof(float) * 2 * nO, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipStreamSynchronize(st));
+        *ms_host_readback = ms_since(t0);
+    }
+    // ... become svo_bundle_adjust's arrays (camera by camera, points numbered by
+    // ascending id: untimed), and stage() sorts and uploads them
+    std::vector<int> oc(P * maxO, 0), op(P * maxO, 0);
+    std::vector<float> oxy(2 * P * maxO, 0.f);
+    for (size_t p = 0; p < P; p++) {
+        std::vector<int> pid;
+        for (int j = 0; j < n_cams; j++)
+            pid.insert(pid.end(), ids + (p * n_cams + j) * cap, ids + (p * n_cams + j) * cap + counts[p * n_cams + j]);
+        std::sort(pid.begin(), pid.end());
+        pid.erase(std::unique(pid.begin(), pid.end()), pid.end());
+        size_t k = p * maxO;
+        for (int j = 0; j < n_cams; j++)
+            for (int q = 0; q < counts[p * n_cams + j]; q++, k++) {
+                const size_t src = (p * n_cams + j) * cap + q;
+                oc[k] = j;
+                op[k] = (int)(std::lower_bound(pid.begin(), pid.end(), ids[src]) - pid.begin());
+                oxy[2 * k] = xy[2 * src];
+                oxy[2 * k + 1] = xy[2 * src + 1];
+            }
+    }
+    const std::vector<double> poses(12 * P * n_cams, 0.0), points(3 * P * maxM, 0.0);
+    const std::vector<uint8_t> fixed(P * n_cams, 1);
+    const Args a{n_problems, n_cams, maxM, maxO, nullptr, h_nm.data(), h_no.data(), poses.data(), fixed.data(),
+                 points.data(), oc.data(), op.data(), oxy.data(), K, 0.0};
+    const auto t0 = clk::now();
+    Staged hs;
+    if ((rc = stage(ctx, a, false, false, hs))) return rc;
+    *ms_host_stage = ms_since(t0);
+    return SVO_OK;
+}
 
 int svo_ba_sort_observations(const int* obs_cam, const int* obs_point, int n_obs, int n_cams, int n_points,
                              int* order, int* pt_off, int* cam_off, int* cam_idx) {
@@ -312,83 +670,9 @@ int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points
     int rc = stage(ctx, a, false, false, s);
     if (rc) return rc;
     const size_t P = (size_t)n_problems;
-    hipStream_t st = ctx->stream;
-    std::vector<double> lambda(P, 1e-4), c_cur(P), c_first(P), c_trial(P), stepinfo(2 * P);
-    std::vector<int> active(P, 1), accept(P), status(P), done(P, 0), its(P, 0);
-    auto read_back = [&]() -> int {
-        SVO_HIP(ctx, hipMemcpyAsync(c_trial.data(), s.tcost, sizeof(double) * P, hipMemcpyDeviceToHost, st));
-        SVO_HIP(ctx, hipMemcpyAsync(stepinfo.data(), s.b.stepinfo, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, st));
-        SVO_HIP(ctx, hipMemcpyAsync(status.data(), s.b.status, sizeof(int) * P, hipMemcpyDeviceToHost, st));
-        SVO_HIP(ctx, hipStreamSynchronize(st));
-        return SVO_OK;
-    };
-    if ((rc = send_control(ctx, s, lambda, active))) return rc;
-    SVO_HIP(ctx, launch_ba_cost(s.b, s.poses, s.points, s.cost, st));
-    SVO_HIP(ctx, hipMemcpyAsync(c_cur.data(), s.cost, sizeof(double) * P, hipMemcpyDeviceToHost, st));
-    SVO_HIP(ctx, hipStreamSynchronize(st));
-    c_first = c_cur;
-    for (int it = 0; it < max_iterations; it++) {
-        bool any = false;
-        for (size_t p = 0; p < P; p++) {
-            active[p] = !done[p];
-            any = any || active[p];
-        }
-        if (!any) break;
-        if ((rc = send_control(ctx, s, lambda, active))) return rc;
-        SVO_HIP(ctx, launch_ba_linearize(s.b, s.poses, s.points, st));
-        if ((rc = launch_solve_chain(ctx, s))) return rc;
-        if ((rc = read_back())) return rc;
-        // reduced system not positive definite: raise lambda and solve again from
-        // the same linearisation, as lm_solve's caller does
-        for (;;) {
-            bool retry = false;
-            for (size_t p = 0; p < P; p++) {
-                const bool again = active[p] && status[p] != 0;
-                if (again) {
-                    lambda[p] *= 10;
-                    if (lambda[p] >= 1e16) {
-                        done[p] = 1;
-                        active[p] = 0;
-                        continue;
-                    }
-                    retry = true;
-                } else if (active[p] && status[p] == 0) {
-                    active[p] = 2;  // solved: waits for the verdict below
-                }
-            }
-            if (!retry) break;
-            std::vector<int> again(P);
-            for (size_t p = 0; p < P; p++) again[p] = active[p] == 1;
-            if ((rc = send_control(ctx, s, lambda, again))) return rc;
-            // V*^-1 depends on lambda, so stage 1 runs again (its camera pass repeats itself)
-            SVO_HIP(ctx, launch_ba_linearize(s.b, s.poses, s.points, st));
-            if ((rc = launch_solve_chain(ctx, s))) return rc;
-            if ((rc = read_back())) return rc;
-        }
-        for (size_t p = 0; p < P; p++) {
-            accept[p] = 0;
-            if (done[p]) continue;
-            its[p]++;
-            if (active[p] != 2) continue;
-            if (std::sqrt(stepinfo[2 * p]) < 1e-12 * (1 + std::sqrt(stepinfo[2 * p + 1]))) {
-                done[p] = 1;
-                continue;
-            }
-            const double c0 = c_cur[p], c1 = c_trial[p];
-            if (c1 <= c0) {
-                accept[p] = 1;
-                c_cur[p] = c1;
-                lambda[p] = lambda[p] * 0.1 > 1e-12 ? lambda[p] * 0.1 : 1e-12;
-                if (c0 - c1 <= 1e-15 * c0) done[p] = 1;
-            } else {
-                lambda[p] *= 10;
-                if (lambda[p] >= 1e16) done[p] = 1;
-            }
-        }
-        SVO_HIP(ctx, hipMemcpyAsync(s.accept, accept.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
-        SVO_HIP(ctx, launch_ba_commit(s.b, s.accept, s.tposes, s.tpoints, s.poses, s.points, st));
-        SVO_HIP(ctx, hipStreamSynchronize(st));
-    }
+    std::vector<double> c_first, c_cur;
+    std::vector<int> its;
+    if ((rc = run_lm(ctx, s, max_iterations, c_first, c_cur, its))) return rc;
     // the device state is the caller's input wherever nothing was accepted
     const size_t nC = P * max_cams, nM = P * max_points;
     std::vector<double> hp(12 * nC), hx(3 * nM);

@@ -356,7 +356,10 @@ __device__ __forceinline__ void tail_body(const TailBatch& T, int s, bool copy_c
     if (mn + take > T.map_cap) {
         map_reclaim<BS>(T.map + 3 * (size_t)s * T.map_cap, T.mid_out + o, n);
         mn = n;
-        if (threadIdx.x == 0) T.map_n[s] = n;
+        if (threadIdx.x == 0) {
+            T.map_n[s] = n;
+            if (T.map_epoch) T.map_epoch[s] += 1;  // the window's older slots name the old ids
+        }
     }
     take = max(min(take, T.map_cap - mn), 0);  // (map_cap >= 2 cap: no bound once reclaimed)
     if (copy_cand) {
@@ -519,7 +522,65 @@ __global__ __launch_bounds__(kFeBlock) void stereo_prep_kernel(StereoPrepBatch B
     if (threadIdx.x == 0) B.spec_n[s] = spec;
 }
 
+// The frame's feature list as the step leaves it into the sequence's ring slot,
+// stamped with the map epoch its ids belong to.
+__global__ __launch_bounds__(kFeBlock) void window_record_kernel(WindowRing R, int slot, const int* __restrict__ n_in,
+                                                                 const float* __restrict__ xy_in,
+                                                                 const int* __restrict__ mid_in) {
+    const int s = blockIdx.x;
+    const int n = min(max(n_in[s], 0), R.cap);
+    const size_t src = (size_t)s * R.cap, dst = ((size_t)s * R.window + slot) * R.cap;
+    const float2* __restrict__ a = (const float2*)xy_in + src;
+    float2* __restrict__ b = (float2*)R.xy + dst;
+    for (int i = threadIdx.x; i < n; i += kFeBlock) {
+        b[i] = a[i];
+        R.mid[dst + i] = mid_in[src + i];
+    }
+    if (threadIdx.x == 0) {
+        R.n[s * R.window + slot] = n;
+        R.epoch[s * R.window + slot] = R.map_epoch[s];
+    }
+}
+
+// One thread per sequence: of the recorded slots (oldest first) those of the
+// map's current epoch become the problem's cameras.
+__global__ __launch_bounds__(64) void window_select_kernel(WindowRing R, WindowOrder O, int nseq,
+                                                           int* __restrict__ sel_slot, int* __restrict__ sel_cnt,
+                                                           int* __restrict__ n_cams) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= nseq) return;
+    const int e = R.map_epoch[s];
+    int v = 0;
+    for (int i = 0; i < O.n; i++) {
+        const int sl = O.slot[i];
+        if (R.epoch[s * R.window + sl] != e) continue;
+        sel_slot[s * R.window + v] = sl;
+        sel_cnt[s * R.window + v] = R.n[s * R.window + sl];
+        v++;
+    }
+    n_cams[s] = v;
+    for (; v < R.window; v++) {
+        sel_slot[s * R.window + v] = 0;
+        sel_cnt[s * R.window + v] = 0;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid, int nseq,
+                                hipStream_t st) {
+    if (slot < 0 || slot >= r.window) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_record_kernel, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_select(const WindowRing& r, const WindowOrder& o, int nseq, int* sel_slot, int* sel_cnt,
+                                int* n_cams, hipStream_t st) {
+    if (o.n < 0 || o.n > r.window || r.window > SVO_BA_MAX_CAMS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_select_kernel, dim3((nseq + 63) / 64), dim3(64), 0, st, r, o, nseq, sel_slot, sel_cnt,
+                       n_cams);
+    return hipGetLastError();
+}
 
 hipError_t launch_post_lk(const PostLkBatch& b, int nseq, hipStream_t st) {
     if (b.nh > 64) return hipErrorInvalidValue;

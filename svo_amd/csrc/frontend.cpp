@@ -13,6 +13,7 @@
 //     drop outliers + the keyframe's first corners       [fe_kernels]    :218-229
 //     stereo LK of those corners into right frame t      [lk.hip]        findLeftFeaturesInRight :94-118
 //     |yR - yL| < 40, DLT triangulation, z > 0, append   [fe_kernels]    triangulateNewMapPoints :120-152
+//     (window enabled) the frame's lists into its ring slot [fe_kernels]  the back end's input, DESIGN.md §10
 //
 // Which frames are keyframes: every frame, topping the set up to n_features
 // (SVO_KF_EVERY, the benchmark), or Tracking::nextFrame's rule (SVO_KF_REFERENCE,
@@ -48,6 +49,7 @@
 #include <thread>
 #include <vector>
 
+#include "ba.hpp"
 #include "frontend.hpp"
 #include "orb.hpp"
 #include "linalg.hpp"
@@ -440,6 +442,15 @@ struct svo_frontend {
     std::vector<hipEvent_t> ev_free;   // [T] the slot's frame f read for the last time (after LK(f + 1))
     std::vector<char> free_rec;        // [T] ev_free recorded since the slot was last queued
     int stepped = -1;                  // last completed step (init: t0); -1 before init
+    // the observation window (svo_frontend_window_enable; win == 0: off, every
+    // pointer below null and nothing added to a step)
+    int win = 0;                 // slots per sequence
+    int win_count = 0;           // frames recorded since init (slot of the next: win_count % win)
+    std::vector<int> win_frame;  // [win] frame number in each slot
+    void* wmem = nullptr;        // device: the ring, the map epochs, the selection
+    WindowRing ring{};
+    int *sel_slot = nullptr, *sel_cnt = nullptr, *sel_nc = nullptr;  // launch_window_select's outputs
+    double* h_wpose = nullptr;   // host-coherent [s][win][12]: the slots' poses, world -> camera
 };
 
 namespace {
@@ -649,6 +660,7 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
     tb.st_xy = fe->st_xy;
     tb.st_n = fe->st_n;
     tb.h_over = fe->h_over;
+    tb.map_epoch = fe->ring.map_epoch;  // (null without a window)
     if (fe->stats_in_tail) {
         // the pending SQPnP statistics of these inliers (the step's bits and points)
         tb.stats_obj = fe->obj_b[fe->stats_parity];
@@ -765,6 +777,37 @@ void fe_set_pose(svo_frontend* fe, int s, bool ok, const double rvec[3], const d
     for (int i = 0; i < 3; i++) T[9 + i] = -(T[3 * i] * tvec[0] + T[3 * i + 1] * tvec[1] + T[3 * i + 2] * tvec[2]);
 }
 
+// The window's slot of frame t: the feature list as the step leaves it (xyA /
+// midA / nA) copied on stream st, which runs behind the frame's keyframe and ahead
+// of whatever rewrites those lists; the slot's pose is the identity until the
+// frame's final fit lands (fe_window_pose). Enqueue only.
+int fe_window_record(svo_frontend* fe, int t, hipStream_t st) {
+    if (!fe->win) return SVO_OK;
+    const int slot = fe->win_count % fe->win;
+    SVO_HIP(fe->ctx, launch_window_record(fe->ring, slot, fe->nA, fe->xyA, fe->midA, fe->S, st));
+    fe->win_frame[slot] = t;
+    fe->win_count++;
+    for (int s = 0; s < fe->S; s++) {
+        double* T = fe->h_wpose + 12 * ((size_t)s * fe->win + slot);
+        for (int q = 0; q < 12; q++) T[q] = (q == 0 || q == 4 || q == 8) ? 1.0 : 0.0;
+    }
+    return SVO_OK;
+}
+
+// The newest slot's poses from the fits that just landed (fe->pose: rvec, tvec;
+// zero without a model): the solvePnPRansac model itself, [R(rvec) | tvec], world
+// -> camera -- the bundle adjustment's convention.
+void fe_window_pose(svo_frontend* fe) {
+    if (!fe->win || fe->win_count == 0) return;
+    const int slot = (fe->win_count - 1) % fe->win;
+    for (int s = 0; s < fe->S; s++) {
+        const double* P = &fe->pose[6 * (size_t)s];
+        double* T = fe->h_wpose + 12 * ((size_t)s * fe->win + slot);
+        la::rodrigues(P, T);
+        std::memcpy(T + 9, P + 3, sizeof(double) * 3);
+    }
+}
+
 // Full D2H of the step's tracked points and map points (after the post-LK), on
 // the copy stream; queued once per step, when first needed or at the step's end.
 int fe_queue_full(svo_frontend* fe) {
@@ -828,6 +871,7 @@ double fe_finish_fits(svo_frontend* fe) {
             fe_set_pose(fe, s, r.ok, P, P + 3);
         });
     }
+    fe_window_pose(fe);
     fe->fits_pending = false;
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -1158,6 +1202,8 @@ void svo_frontend_destroy(svo_frontend* fe) {
     if (fe->up_stage) (void)hipFree(fe->up_stage);
     orb_batch_destroy(fe->orb);
     if (fe->fit_work) (void)hipFree(fe->fit_work);
+    if (fe->wmem) (void)hipFree(fe->wmem);
+    if (fe->h_wpose) (void)hipHostFree(fe->h_wpose);
     delete fe;
 }
 
@@ -1354,10 +1400,15 @@ int svo_frontend_init(svo_frontend* fe, int t0) {
     SVO_HIP(ctx, hipMemsetAsync(fe->nA, 0, sizeof(int) * S, ctx->stream));
     SVO_HIP(ctx, hipMemsetAsync(fe->map_n, 0, sizeof(int) * S, ctx->stream));
     SVO_HIP(ctx, hipMemsetAsync(fe->pend_n, 0, sizeof(int) * S, ctx->stream));
+    if (fe->win) SVO_HIP(ctx, hipMemsetAsync(fe->ring.map_epoch, 0, sizeof(int) * S, ctx->stream));
     int rc = fe->orb ? fe_orb_detect(fe, t0, false, ctx->stream) : fe_fast_and_bucket(fe, dcur, false, ctx->stream);
     if (rc) return rc;
     // n_in = nA (zero): nothing to compact, the candidates fill the set
     rc = fe_keyframe(fe, t0, fe->nA, nullptr, fe->xyA, fe->midA, fe->cfg.n_features, ctx->stream);
+    if (rc) return rc;
+    // the window starts over with frame t0 (its map ids start from 0 again)
+    fe->win_count = 0;
+    rc = fe_window_record(fe, t0, ctx->stream);
     if (rc) return rc;
     for (int s = 0; s < S; s++) fe_set_pose(fe, s, false, nullptr, nullptr);
     SVO_HIP(ctx, launch_finalize_map(fe_pending(fe), S, ctx->stream));
@@ -1671,7 +1722,9 @@ int svo_frontend_step(svo_frontend* fe, int t, svo_frontend_stats* stats) {
     // points to the world frame, so this step's post-LK is queued right after
     // (with device_fits they ran on the device and the post-LK waits there)
     ms_enqueue += ms_since(t_call);
-    double ms_fit = fe->device_fits ? 0.0 : fe_finish_fits(fe);
+    // (a window needs the device's fits on the host too, before this step's frame
+    // takes the next slot: they ran behind the last step's keyframe)
+    double ms_fit = fe->device_fits && !fe->win ? 0.0 : fe_finish_fits(fe);
     TP("fits done");
     {
         const auto te = clk::now();
@@ -1955,6 +2008,11 @@ int svo_frontend_step(svo_frontend* fe, int t, svo_frontend_stats* stats) {
     // keyframe; only the SQPnP statistics of these inliers go to the GPU ahead of
     // it (the pose fits need them at the next step's start).
     SVO_HIP(ctx, hipStreamWaitEvent(sf, fe->ev_tail, 0));
+    // the window's copy of this frame's lists, on the FAST stream behind the
+    // keyframe: the next keyframe, which rewrites them, waits for that stream's
+    // FAST chain (ev_fast) queued behind this copy
+    rc = fe_window_record(fe, t, sf);
+    if (rc) return rc;
     // this step's counts, before the next step's first half re-fills the mirrors
     int64_t lk_its = 0, tracked = 0;
     for (int s = 0; s < S; s++) {
@@ -2098,6 +2156,119 @@ int svo_frontend_map_points(svo_frontend* fe, int seq, double* xyz, int cap, int
     }
     if (n) *n = cnt;
     return SVO_OK;
+}
+
+int svo_frontend_window_enable(svo_frontend* fe, int window) {
+    if (!fe) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (window < 1 || window > SVO_BA_MAX_CAMS)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable: window outside 1 .. SVO_BA_MAX_CAMS");
+    if (fe->stepped >= 0 || fe->win)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable: once, before svo_frontend_init");
+    const size_t S = fe->S, Wn = window, CAP = fe->CAP;
+    size_t bytes = 0;
+    char* const base0 = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && hipMalloc(&fe->wmem, bytes) != hipSuccess) {
+            fe->wmem = nullptr;
+            fe->ring = WindowRing{};  // (the sizing pass left offsets in it)
+            return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: hipMalloc(%zu)", bytes);
+        }
+        char* p = pass == 0 ? base0 : (char*)fe->wmem;
+        fe->ring.window = window;
+        fe->ring.cap = fe->CAP;
+        fe->ring.n = carve<int>(p, S * Wn);
+        fe->ring.epoch = carve<int>(p, S * Wn);
+        fe->ring.xy = carve<float>(p, 2 * S * Wn * CAP);
+        fe->ring.mid = carve<int>(p, S * Wn * CAP);
+        fe->ring.map_epoch = carve<int>(p, S);
+        fe->sel_slot = carve<int>(p, S * Wn);
+        fe->sel_cnt = carve<int>(p, S * Wn);
+        fe->sel_nc = carve<int>(p, S);
+        bytes = (size_t)(p - (pass == 0 ? base0 : (char*)fe->wmem)) + 256;
+    }
+    if (hipHostMalloc((void**)&fe->h_wpose, sizeof(double) * 12 * S * Wn, hipHostMallocCoherent | hipHostMallocMapped) !=
+        hipSuccess) {
+        (void)hipFree(fe->wmem);
+        fe->wmem = nullptr;
+        fe->h_wpose = nullptr;
+        fe->ring = WindowRing{};
+        return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: host-coherent poses");
+    }
+    std::memset(fe->h_wpose, 0, sizeof(double) * 12 * S * Wn);
+    SVO_HIP(ctx, hipMemsetAsync(fe->wmem, 0, bytes, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fe->win_frame.assign(Wn, -1);
+    fe->win_count = 0;
+    fe->win = window;
+    return SVO_OK;
+}
+
+// the recorded slots, oldest first
+static WindowOrder fe_window_order(const svo_frontend* fe) {
+    WindowOrder o{};
+    o.n = std::min(fe->win_count, fe->win);
+    for (int i = 0; i < o.n; i++) o.slot[i] = (fe->win_count - o.n + i) % fe->win;
+    return o;
+}
+
+int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* frame_t, double* poses, int* counts,
+                        int* ids, float* xy) {
+    if (!fe || seq < 0 || seq >= fe->S || cap < 0) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (!fe->win) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window: no window enabled");
+    int rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    const size_t Wn = fe->win, CAP = fe->CAP;
+    std::vector<int> n(Wn), ep(Wn);
+    int cur = 0;
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(n.data(), fe->ring.n + seq * Wn, sizeof(int) * Wn, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(ep.data(), fe->ring.epoch + seq * Wn, sizeof(int) * Wn, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(&cur, fe->ring.map_epoch + seq, sizeof(int), hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    const WindowOrder o = fe_window_order(fe);
+    int v = 0;
+    for (int i = 0; i < o.n; i++) {
+        const int sl = o.slot[i];
+        if (ep[sl] != cur) continue;  // recorded before the map's last reclaim
+        const int k = std::min(n[sl], cap);
+        const size_t src = (seq * Wn + sl) * CAP;
+        if (frame_t) frame_t[v] = fe->win_frame[sl];
+        if (counts) counts[v] = k;
+        if (poses) std::memcpy(poses + 12 * (size_t)v, fe->h_wpose + 12 * (seq * Wn + sl), sizeof(double) * 12);
+        if (ids && k > 0)
+            SVO_HIP(ctx, hipMemcpyAsync(ids + (size_t)v * cap, fe->ring.mid + src, sizeof(int) * k, hipMemcpyDeviceToHost, st));
+        if (xy && k > 0)
+            SVO_HIP(ctx, hipMemcpy(xy + 2 * (size_t)v * cap, fe->ring.xy + 2 * src, sizeof(float) * 2 * k,
+                                   hipMemcpyDeviceToHost));
+        v++;
+    }
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    if (n_frames) *n_frames = v;
+    return SVO_OK;
+}
+
+int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations, double* costs,
+                               int* iterations, int* sizes) {
+    if (!fe) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (!fe->win) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_bundle_adjust: no window enabled");
+    if (n_fixed < 0 || max_iterations < 0)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_bundle_adjust: n_fixed / max_iterations < 0");
+    // the newest frame's pose lands and its keyframe's points reach the world frame
+    int rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    SVO_HIP(ctx, launch_window_select(fe->ring, fe_window_order(fe), fe->S, fe->sel_slot, fe->sel_cnt, fe->sel_nc,
+                                      ctx->stream));
+    BaDeviceWindow w;
+    w.lists = BaLists{fe->S, fe->win, fe->CAP, fe->sel_slot, fe->sel_cnt, fe->ring.mid, fe->ring.xy};
+    w.n_cams = fe->sel_nc;
+    w.ring = fe->h_wpose;
+    w.map = fe->map;
+    w.map_cap = fe->MAPCAP;
+    w.n_fixed = n_fixed;
+    return ba_adjust_device(ctx, w, fe->cfg.K, huber_delta, max_iterations, costs, iterations, sizes);
 }
 
 int svo_frontend_scharr_level(svo_frontend* fe, int seq, int t, int level, int16_t* ix, int16_t* iy, int stride) {

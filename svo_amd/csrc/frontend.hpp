@@ -90,6 +90,9 @@ struct TailBatch {
     const float* stats_obj = nullptr;
     double* stats_out = nullptr;
     double ifx = 0, ify = 0, cx = 0, cy = 0;
+    // nullable: [s], incremented when the keyframe reclaims the sequence's map
+    // (the observation window's slots remember the epoch of their ids)
+    int* map_epoch = nullptr;
 };
 hipError_t launch_tail(const TailBatch& tb, int nseq, hipStream_t st);
 
@@ -162,5 +165,31 @@ hipError_t launch_stereo_tri(const StereoTriBatch& b, int nseq, int max_n, hipSt
 // LK covered every sequence's take (st_next / st_status already hold the matches
 // of st_xy[0, take)); same results as the two kernels with the LK between them.
 hipError_t launch_keyframe_fused(const TailBatch& tb, const AppendBatch& ab, int nseq, hipStream_t st);
+
+// The observation window (svo_frontend_window_enable): per sequence a ring of
+// `window` slots, each a frame's feature list -- n, xy[cap], mid[cap] -- and the
+// map epoch it was recorded in. map_epoch[s] counts the reclaims of sequence s's
+// map (TailBatch): a reclaim renumbers the ids, so slots of an older epoch are
+// skipped by every reader.
+struct WindowRing {
+    int window, cap;
+    int* n;          // [s][window]
+    int* epoch;      // [s][window]
+    float* xy;       // [s][window][cap][2]
+    int* mid;        // [s][window][cap], strictly increasing per slot
+    int* map_epoch;  // [s]
+};
+// xyA / midA / nA as the step leaves them into `slot` of every sequence
+hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid, int nseq,
+                                hipStream_t st);
+// The recorded slots, oldest first (the same for every sequence: the ring turns
+// in lockstep); per sequence those of the current epoch are valid:
+// sel_slot / sel_cnt [s][window] (the valid slots first, zero counts behind), n_cams [s].
+struct WindowOrder {
+    int n;
+    int slot[SVO_BA_MAX_CAMS];
+};
+hipError_t launch_window_select(const WindowRing& r, const WindowOrder& o, int nseq, int* sel_slot, int* sel_cnt,
+                                int* n_cams, hipStream_t st);
 
 }  // namespace svo

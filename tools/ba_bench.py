@@ -3,6 +3,8 @@
 (svo_ba_time_iteration: linearise, eliminate, solve, update, trial cost; HIP
 events after one warm-up) on the batched front end's use case: 256 problems x 8
 cameras x 2000 points with about 70 % of the possible observations present.
+--stage: the device staging chain for the same use case given as the front end's
+window holds it (svo_ba_time_staging), against the host's staging of those lists.
 Prints one JSON line. Not a test and not the project's benchmark (bench.py)."""
 import argparse
 import json
@@ -43,8 +45,41 @@ def problems(P, C, M, present, seed):
     return poses, fixed, X, oc, op, oxy, n_obs
 
 
+def window_lists(P, C, M, present, seed):
+    """The same use case as the front end's window holds it: per problem and camera a
+    list of the point ids it sees, ascending, with their pixels (cap: M rounded up
+    to 64, the front end's feature capacity)."""
+    rng = np.random.default_rng(seed)
+    cap = (M + 63) // 64 * 64
+    keep = rng.random((P, C, M)) < present
+    counts = keep.sum(2).astype(np.int32)
+    ids = np.zeros((P, C, cap), np.int32)
+    xy = np.zeros((P, C, cap, 2), np.float32)
+    for p in range(P):
+        for j in range(C):
+            i = np.nonzero(keep[p, j])[0]
+            ids[p, j, :len(i)] = i
+            xy[p, j, :len(i)] = rng.uniform(0, 1200, (len(i), 2))
+    return counts, ids, xy
+
+
+def stage_main(a):
+    """--stage: the device staging chain against the host's staging of the same windows."""
+    counts, ids, xy = window_lists(a.problems, a.cams, a.points, a.present, 0)
+    ctx = S.Context(0)
+    ms = ctx.ba_time_staging(counts, ids, xy, reps=a.reps)
+    print(json.dumps({"name": "ba_staging", "problems": a.problems, "cams": a.cams, "points": a.points,
+                      "observations": int(counts.sum()), "reps": a.reps,
+                      "ms_device_chain": round(ms["ms_device"], 4),
+                      "ms_host_readback": round(ms["ms_host_readback"], 3),
+                      "ms_host_sort_and_upload": round(ms["ms_host_stage"], 3),
+                      "list_bytes": int(ids.nbytes + xy.nbytes + counts.nbytes)}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--stage", action="store_true",
+                    help="time the device staging chain (svo_ba_time_staging) instead of the LM iteration")
     ap.add_argument("--problems", type=int, default=256)
     ap.add_argument("--cams", type=int, default=8)
     ap.add_argument("--points", type=int, default=2000)
@@ -52,6 +87,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--huber", type=float, default=2.0)
     a = ap.parse_args()
+    if a.stage:
+        return stage_main(a)
     poses, fixed, X, oc, op, oxy, n_obs = problems(a.problems, a.cams, a.points, a.present, 0)
     ctx = S.Context(0)
     ms = ctx.ba_time_iteration(poses, fixed, X, oc, op, oxy, K, lam=1e-4, huber_delta=a.huber, reps=a.reps,
