@@ -249,21 +249,31 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
  * monocular observations in any order (obs_cam / obs_point: indices within the
  * problem, obs_xy: 2 floats). n_cams / n_points / n_obs: P counts each, or NULL
  * = the maximum. Residual, Huber weight, cost and the Pz <= 0 rule per
- * observation are those of svo_reprojection_jacobians. A point seen by fewer
- * than two cameras in front of it is held constant (its observations still
- * constrain their cameras), so is a point whose damped 3x3 block is not
- * positive definite (for that iteration); a free camera with no observation in
- * front of it is treated as fixed. Every stage runs on the device with a fixed
- * summation order: the results do not depend on the order of the observations
- * beyond a stable sort by (point, camera), and two runs give the same bits.
- * SVO_ERR_ARG (nothing written): sizes or counts out of range, max_cams above
- * SVO_BA_MAX_CAMS, an observation naming a camera or point outside its problem,
- * NULL where data is required. */
+ * observation are those of svo_reprojection_jacobians. A camera may observe a
+ * point more than once: every observation enters the sums (one W_ij per pair),
+ * and together they count as one camera. A point seen by fewer than two distinct
+ * cameras in front of it is held constant (its observations still constrain
+ * their cameras; two observations by one camera give no depth), so is a point
+ * whose damped 3x3 block is not positive definite (for that iteration); a free
+ * camera with no observation in front of it is treated as fixed. Every stage runs
+ * on the device with a fixed summation order: the results do not depend on the
+ * order of the observations beyond a stable sort by (point, camera), and two
+ * runs give the same bits. SVO_ERR_ARG (nothing written): sizes or counts out of
+ * range, max_cams above SVO_BA_MAX_CAMS, an observation naming a camera or point
+ * outside its problem, NULL where data is required. */
 #define SVO_BA_MAX_CAMS 16
 /* Levenberg-Marquardt (svo_refine_poses' control: lambda from 1e-4, x0.1 down to
  * 1e-12 on success, x10 on failure up to 1e16, the same stopping rules), per
  * problem. poses, points: in/out. costs: P x 2 (initial, final), iterations: P
- * (LM iterations each problem took); both may be NULL. */
+ * (LM iterations each problem began: one that ends because the reduced system
+ * stays not positive definite up to lambda = 1e16, or on the step-size rule,
+ * counts like one that ends in a verdict); both may be NULL. Values that are not
+ * finite are not an error (the call returns SVO_OK) and stay within their
+ * problem: a problem with a NaN or an infinity among its poses, points or
+ * observations (within its counts), or whose initial cost is not finite, is not
+ * iterated on. Its poses and points come back with the bits they came with, both
+ * its costs are NaN and its iteration count is 0; the other problems of the batch
+ * get what they get alone. */
 int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
                       const int* n_points, const int* n_obs, double* poses, const uint8_t* fixed, double* points,
                       const int* obs_cam, const int* obs_point, const float* obs_xy, const double K[9],
@@ -277,7 +287,9 @@ int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points
  * W_ij V*_i^-1 W_ik^T and b (P x 6 max_cams) = -gc + sum_i W_ij V*_i^-1 gp_i. The
  * step: dc (P*max_cams*6, zero for cameras outside the reduced system), dp
  * (P*max_points*3, zero for constant points); status (P): 1 = S not positive
- * definite (dc and dp are zero). */
+ * definite (dc and dp are zero; S and b are returned all the same). Values that
+ * are not finite are not looked for here: they give what IEEE arithmetic gives,
+ * within their problem. */
 int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
                      const int* n_points, const int* n_obs, const double* poses, const uint8_t* fixed,
                      const double* points, const int* obs_cam, const int* obs_point, const float* obs_xy,
@@ -500,7 +512,9 @@ int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* 
  * iterations: S, sizes: S*3 (frames, points, observations); any may be NULL.
  * The results equal svo_bundle_adjust's, bit for bit, on the same window given
  * frame by frame with the points numbered by ascending map id and max_points /
- * max_obs the batch's largest counts. A sequence with an empty or one-frame window
+ * max_obs the batch's largest counts (finite values: the window is never read
+ * on the host, so of svo_bundle_adjust's rule for values that are not finite
+ * only "initial cost not finite" applies). A sequence with an empty or one-frame window
  * is a valid problem in which nothing is free: it comes back unchanged.
  * Synchronises the front end first. SVO_ERR_ARG: window not enabled, n_fixed < 0,
  * max_iterations < 0. */

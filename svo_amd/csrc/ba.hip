@@ -13,10 +13,11 @@
 //   5 cost        of the trial state (stage 1's camera pass, cost only)
 // Every sum has a fixed order (a thread's own items in index order, wave
 // shuffles, LDS, then partials in index order) and nothing is accumulated with
-// atomics, so two runs give the same bits. Points seen by fewer than two cameras
-// in front of them, and points whose damped block is not positive definite, are
-// held constant; a free camera with no observation in front of it is treated as
-// fixed.
+// atomics, so two runs give the same bits. A camera may observe a point more than
+// once: the observations are summed (one W_ij) and count as one camera. Points
+// seen by fewer than two cameras in front of them, and points whose damped block
+// is not positive definite, are held constant; a free camera with no observation
+// in front of it is treated as fixed.
 #include "ba.hpp"
 
 namespace svo {
@@ -166,12 +167,14 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BaBatch d, const double* 
     const double* X = points + 3 * pi;
     const int o0 = d.pt_off[(size_t)p * (d.maxM + 1) + i], o1 = d.pt_off[(size_t)p * (d.maxM + 1) + i + 1];
     double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
-    int nfront = 0;
+    int nfront = 0, prev = -1;  // distinct cameras in front: a camera's observations are consecutive
     for (int a = o0; a < o1; a++) {
-        const double* T = poses + 12 * ((size_t)p * d.maxC + d.ocam[ob + a]);
+        const int cam = d.ocam[ob + a];
+        const double* T = poses + 12 * ((size_t)p * d.maxC + cam);
         double r0, r1, w, c, J[12], Jp[6];
         if (!obs_eval(k, T, X, d.oxy + 2 * (ob + a), r0, r1, w, c, J)) continue;
-        nfront++;
+        nfront += cam != prev;
+        prev = cam;
         point_jacobian(J, T, Jp);
         int q = 0;
 #pragma unroll

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "ba.hpp"
@@ -241,11 +242,28 @@ int launch_solve_chain(svo_ctx* ctx, Staged& s) {
     return SVO_OK;
 }
 
+// Per problem: does it hold a value that is not finite (within its counts)?
+std::vector<uint8_t> non_finite(const Args& a) {
+    std::vector<uint8_t> bad((size_t)a.P, 0);
+    for (size_t p = 0; p < (size_t)a.P; p++) {
+        const int C = a.n_cams ? a.n_cams[p] : a.maxC, M = a.n_points ? a.n_points[p] : a.maxM;
+        const int O = a.n_obs ? a.n_obs[p] : a.maxO;
+        bool ok = true;
+        for (int q = 0; q < 12 * C && ok; q++) ok = std::isfinite(a.poses[12 * p * a.maxC + q]);
+        for (int q = 0; q < 3 * M && ok; q++) ok = std::isfinite(a.points[3 * p * a.maxM + q]);
+        for (int q = 0; q < 2 * O && ok; q++) ok = std::isfinite(a.obs_xy[2 * p * a.maxO + q]);
+        bad[p] = !ok;
+    }
+    return bad;
+}
+
 // svo_bundle_adjust's Levenberg-Marquardt control over a filled block: the
 // refined state stays in s.poses / s.points. c_first / c_cur: the initial and the
-// final cost, its: the iterations each problem took.
-int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, std::vector<double>& c_first, std::vector<double>& c_cur,
-           std::vector<int>& its) {
+// final cost, its: the iterations each problem began. A problem the caller marks
+// in `bad` (empty: none), or whose initial cost is not finite, is not iterated on:
+// its state is never written, its costs are NaN and its count 0.
+int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, const std::vector<uint8_t>& bad,
+           std::vector<double>& c_first, std::vector<double>& c_cur, std::vector<int>& its) {
     const size_t P = (size_t)s.b.P;
     int rc;
     hipStream_t st = ctx->stream;
@@ -264,12 +282,18 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, std::vector<double>& c_f
     SVO_HIP(ctx, launch_ba_cost(s.b, s.poses, s.points, s.cost, st));
     SVO_HIP(ctx, hipMemcpyAsync(c_cur.data(), s.cost, sizeof(double) * P, hipMemcpyDeviceToHost, st));
     SVO_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t p = 0; p < P; p++)
+        if ((!bad.empty() && bad[p]) || !std::isfinite(c_cur[p])) {
+            done[p] = 1;
+            c_cur[p] = std::numeric_limits<double>::quiet_NaN();
+        }
     c_first = c_cur;
     for (int it = 0; it < max_iterations; it++) {
         bool any = false;
         for (size_t p = 0; p < P; p++) {
             active[p] = !done[p];
             any = any || active[p];
+            its[p] += active[p];  // begun: it counts even if it gives up below
         }
         if (!any) break;
         if ((rc = send_control(ctx, s, lambda, active))) return rc;
@@ -305,9 +329,7 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, std::vector<double>& c_f
         }
         for (size_t p = 0; p < P; p++) {
             accept[p] = 0;
-            if (done[p]) continue;
-            its[p]++;
-            if (active[p] != 2) continue;
+            if (done[p] || active[p] != 2) continue;
             if (std::sqrt(stepinfo[2 * p]) < 1e-12 * (1 + std::sqrt(stepinfo[2 * p + 1]))) {
                 done[p] = 1;
                 continue;
@@ -430,7 +452,7 @@ int svo::ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[
     SVO_HIP(ctx, launch_ba_stage_cams(l, w.n_cams, w.ring, w.n_fixed, s.poses, s.fixed, st));
     std::vector<double> c_first, c_cur;
     std::vector<int> its;
-    if ((rc = run_lm(ctx, s, max_iterations, c_first, c_cur, its))) return rc;
+    if ((rc = run_lm(ctx, s, max_iterations, {}, c_first, c_cur, its))) return rc;
     SVO_HIP(ctx, launch_ba_stage_unstage(l, w.n_cams, s.n_points, s.pt_id, maxM, s.points, s.poses, s.fixed, w.map,
                                          w.map_cap, w.ring, st));
     SVO_HIP(ctx, hipStreamSynchronize(st));
@@ -672,7 +694,7 @@ int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points
     const size_t P = (size_t)n_problems;
     std::vector<double> c_first, c_cur;
     std::vector<int> its;
-    if ((rc = run_lm(ctx, s, max_iterations, c_first, c_cur, its))) return rc;
+    if ((rc = run_lm(ctx, s, max_iterations, non_finite(a), c_first, c_cur, its))) return rc;
     // the device state is the caller's input wherever nothing was accepted
     const size_t nC = P * max_cams, nM = P * max_points;
     std::vector<double> hp(12 * nC), hx(3 * nM);
