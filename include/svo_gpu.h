@@ -137,6 +137,15 @@ typedef struct svo_orb_params {
 } svo_orb_params;
 int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params,
                    const uint8_t* mask, svo_keypoint* out, int* octave, int cap, int* n_out);
+/* Test and debug only (parity tests of the scale and mask pyramids): builds the
+ * pyramids exactly as svo_orb_detect does, by the same code, and copies out level
+ * `level`: out_img lw*lh u8 (tight rows), out_mask the same or NULL (left unwritten
+ * without a mask). Level 0 is the caller's image and mask; the masks of levels
+ * 1.. are thresholded (255 or 0). *lw, *lh: the level's size (either may be NULL;
+ * out_img must hold at least W*H bytes if the size is not known beforehand).
+ * SVO_ERR_ARG: level outside [0, nlevels), or parameters svo_orb_detect rejects. */
+int svo_orb_level(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, const uint8_t* mask,
+                  int level, uint8_t* out_img, uint8_t* out_mask, int* lw, int* lh);
 
 /* R:src/tracking.cpp:76-79: W*H mask of 255 with a filled box of +-half around
  * each point (cvRound corners, inclusive, clipped). Host output. */

@@ -107,6 +107,7 @@ _SIGS = [
     ("svo_image_scharr_level", C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int16), C.POINTER(C.c_int16), C.c_int]),
     ("svo_fast_detect", C.c_int, [_vp, _vp, C.c_int, C.c_int, _u8p, _f32p, C.c_int, _i32p]),
     ("svo_orb_detect", C.c_int, [_vp, _vp, _vp, _u8p, _f32p, _i32p, C.c_int, _i32p]),
+    ("svo_orb_level", C.c_int, [_vp, _vp, _vp, _u8p, C.c_int, _u8p, _u8p, _i32p, _i32p]),
     ("svo_fast_score_map", C.c_int, [_vp, _vp, C.c_int, _u8p, _u8p]),
     ("svo_mask_boxes", C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_float, _u8p]),
     ("svo_bucket_features", C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -426,6 +427,24 @@ class Context:
                                          _p(octv, _i32p), cap, C.byref(n)))
         k = min(n.value, cap)
         return out[:k].copy(), octv[:k].copy()
+
+    def orb_level(self, img: Image, params: "OrbParams" = None, mask=None, level: int = 0):
+        """Test and debug only (svo_orb_level): level `level` of the scale pyramid
+        svo_orb_detect builds, and of its mask pyramid -> (image, mask or None)."""
+        params = params or OrbParams()
+        out = np.empty(img.h * img.w, np.uint8)  # no level is larger than level 0
+        om = mp = None
+        if mask is not None:
+            mask = _c(mask, np.uint8)
+            assert mask.shape == (img.h, img.w)
+            mp = _p(mask, _u8p)
+            om = np.empty(img.h * img.w, np.uint8)
+        lw, lh = C.c_int(), C.c_int()
+        self._check(lib().svo_orb_level(self.handle, img.handle, C.byref(params), mp, int(level), _p(out, _u8p),
+                                        None if om is None else _p(om, _u8p), C.byref(lw), C.byref(lh)))
+        n = lw.value * lh.value
+        shape = (lh.value, lw.value)
+        return out[:n].reshape(shape).copy(), None if om is None else om[:n].reshape(shape).copy()
 
     def fast_score_map(self, img: Image, threshold: int = 20):
         score = np.empty((img.h, img.w), np.uint8)

@@ -390,19 +390,36 @@ hipError_t orb_batch_detect(OrbBatch* ob, const ImgLevel* lv0, const float* box_
 
 using namespace svo;
 
-extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
-                              svo_keypoint* out, int* octave, int cap, int* n_out) {
-    if (!ctx || !img || !prm || (!out && cap > 0) || cap < 0)
-        return set_error(ctx, SVO_ERR_ARG, "svo_orb_detect: bad arguments");
+namespace {
+
+// svo_orb_detect's workspace and the scale and mask pyramids built in it
+struct OrbLevels {
+    OrbGeometry g;
+    size_t mask_off[kMaxLevels];
+    PyrDesc lev;             // the levels (level 0 = the caller's image)
+    uint8_t* dmask;          // level masks at mask_off[l] (rows of lw[l]); null without a mask
+    PyrDesc* ddesc;          // device: [l].lv[0] = level l
+    unsigned long long* bits;
+    int *rowcnt, *rowoff;
+    svo_keypoint* dkp;       // [nlev][maxcap]
+    int* dn;
+    float* dresp;            // [nlev][maxcap]
+};
+
+// The pyramid half of svo_orb_detect, shared with svo_orb_level: level geometry,
+// workspace layout, upload of the coefficient tables, the level descriptors and
+// the mask, and the scale + mask pyramids (queued on the context's stream).
+int orb_build_levels(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
+                     const char* who, OrbLevels& o) {
     hipStream_t st = ctx->stream;
     const ImgLevel& L0 = img->desc.lv[0];
     const int W = L0.w, H = L0.h;
-    OrbGeometry g;
+    OrbGeometry& g = o.g;
     const char* why = nullptr;
-    if (!orb_geometry(W, H, *prm, g, &why))
-        return set_error(ctx, SVO_ERR_ARG, "svo_orb_detect: %s", why);
+    if (!orb_geometry(W, H, *prm, g, &why)) return set_error(ctx, SVO_ERR_ARG, "%s: %s", who, why);
     const int nlev = g.nlev;
-    size_t img_off[kMaxLevels], mask_off[kMaxLevels];
+    size_t img_off[kMaxLevels];
+    size_t* mask_off = o.mask_off;
     size_t ibytes = 0, mbytes = 0;
     for (int l = 0; l < nlev; l++) {
         img_off[l] = ibytes;
@@ -428,21 +445,25 @@ extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_
                  o_resp = take(sizeof(float) * (size_t)nlev * maxcap), o_tab = take(sizeof(uint32_t) * tab_words),
                  o_desc = take(sizeof(PyrDesc) * (kMaxLevels + 1));
     char* ws = (char*)scratch(ctx, 10, off);
-    if (!ws) return set_error(ctx, SVO_ERR_HIP, "svo_orb_detect: workspace alloc failed");
+    if (!ws) return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
     uint8_t* dimg = (uint8_t*)(ws + o_img);
-    uint8_t* dmask = mask ? (uint8_t*)(ws + o_mask) : nullptr;
-    svo_keypoint* dkp = (svo_keypoint*)(ws + o_kp);
-    int* dn = (int*)(ws + o_n);
-    float* dresp = (float*)(ws + o_resp);
+    uint8_t* dmask = o.dmask = mask ? (uint8_t*)(ws + o_mask) : nullptr;
+    o.dkp = (svo_keypoint*)(ws + o_kp);
+    o.dn = (int*)(ws + o_n);
+    o.dresp = (float*)(ws + o_resp);
+    o.bits = (unsigned long long*)(ws + o_bits);
+    o.rowcnt = (int*)(ws + o_rc);
+    o.rowoff = o.rowcnt + maxh + 64;
     // levels as pyramid descriptors (level 0 = the caller's image)
-    PyrDesc lev{};
+    PyrDesc& lev = o.lev;
+    lev = PyrDesc{};
     lev.nlevels = nlev;
     for (int l = 0; l < nlev; l++)
         lev.lv[l] = l == 0 ? L0 : ImgLevel{dimg + img_off[l], g.lw[l], g.lh[l], g.pitch[l]};
     // host staging: tables, per-level descriptors (lv[0] = that level)
     const size_t stage_bytes = sizeof(uint32_t) * tab_words + sizeof(PyrDesc) * kMaxLevels;
     char* hst = (char*)pinned(ctx, stage_bytes + 64);
-    if (!hst) return set_error(ctx, SVO_ERR_HIP, "svo_orb_detect: pinned alloc failed");
+    if (!hst) return set_error(ctx, SVO_ERR_HIP, "%s: pinned alloc failed", who);
     SVO_HIP(ctx, hipStreamSynchronize(st));  // the pinned buffer may still feed an earlier copy
     if (tab_words) std::memcpy(hst, g.tabs.data(), sizeof(uint32_t) * tab_words);
     PyrDesc* hdesc = (PyrDesc*)(hst + sizeof(uint32_t) * tab_words);
@@ -453,7 +474,7 @@ extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_
         std::memcpy(&hdesc[l], &d, sizeof(d));
     }
     uint32_t* dtab = (uint32_t*)(ws + o_tab);
-    PyrDesc* ddesc = (PyrDesc*)(ws + o_desc);
+    PyrDesc* ddesc = o.ddesc = (PyrDesc*)(ws + o_desc);
     if (tab_words) SVO_HIP(ctx, hipMemcpyAsync(dtab, hst, sizeof(uint32_t) * tab_words, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(ddesc, hdesc, sizeof(PyrDesc) * nlev, hipMemcpyHostToDevice, st));
     if (mask) SVO_HIP(ctx, hipMemcpyAsync(dmask, mask, (size_t)W * H, hipMemcpyHostToDevice, st));
@@ -465,10 +486,51 @@ extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_
                                        dmask ? dmask + mask_off[l] : nullptr, g.lw[l], g.lh[l], (const int*)t,
                                        t + g.lw[l], (const int*)(t + 2 * g.lw[l]), t + 2 * g.lw[l] + g.lh[l], st));
     }
+    return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" int svo_orb_level(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
+                             int level, uint8_t* out_img, uint8_t* out_mask, int* lw, int* lh) {
+    if (!ctx || !img || !prm || !out_img) return set_error(ctx, SVO_ERR_ARG, "svo_orb_level: bad arguments");
+    if (level < 0 || level >= prm->nlevels) return set_error(ctx, SVO_ERR_ARG, "svo_orb_level: no such level");
+    OrbLevels o;
+    const int rc = orb_build_levels(ctx, img, prm, mask, "svo_orb_level", o);
+    if (rc != SVO_OK) return rc;
+    hipStream_t st = ctx->stream;
+    const ImgLevel& L = o.lev.lv[level];
+    SVO_HIP(ctx, hipMemcpy2DAsync(out_img, L.w, L.data, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, st));
+    if (out_mask && o.dmask)
+        SVO_HIP(ctx, hipMemcpyAsync(out_mask, o.dmask + o.mask_off[level], (size_t)L.w * L.h, hipMemcpyDeviceToHost,
+                                    st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    if (lw) *lw = L.w;
+    if (lh) *lh = L.h;
+    return SVO_OK;
+}
+
+extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
+                              svo_keypoint* out, int* octave, int cap, int* n_out) {
+    if (!ctx || !img || !prm || (!out && cap > 0) || cap < 0)
+        return set_error(ctx, SVO_ERR_ARG, "svo_orb_detect: bad arguments");
+    OrbLevels o;
+    const int rc = orb_build_levels(ctx, img, prm, mask, "svo_orb_detect", o);
+    if (rc != SVO_OK) return rc;
+    hipStream_t st = ctx->stream;
+    const OrbGeometry& g = o.g;
+    const int nlev = g.nlev, maxcap = g.maxcap;
+    const size_t* mask_off = o.mask_off;
+    const PyrDesc& lev = o.lev;
+    uint8_t* dmask = o.dmask;
+    PyrDesc* ddesc = o.ddesc;
+    svo_keypoint* dkp = o.dkp;
+    int* dn = o.dn;
+    float* dresp = o.dresp;
     // FAST(fastThreshold, NMS) + the level mask, per level
-    unsigned long long* bits = (unsigned long long*)(ws + o_bits);
-    int* rowcnt = (int*)(ws + o_rc);
-    int* rowoff = rowcnt + maxh + 64;
+    unsigned long long* bits = o.bits;
+    int* rowcnt = o.rowcnt;
+    int* rowoff = o.rowoff;
     const int thr = std::min(std::max(prm->fast_threshold, 0), 255);
     for (int l = 0; l < nlev; l++) {
         FastDetBatch b{ddesc + l, dmask ? dmask + mask_off[l] : nullptr, bits, rowcnt, rowoff,

@@ -7,7 +7,9 @@ reduction is the rounded 2x2 mean, constants stay constant, a linear ramp stays 
 ramp), ORB's level schedule for the KITTI size (sizes, float scales, features per
 level), and properties of the oracle's detection (every keypoint is a FAST corner
 of its level, inside the edge, outside the mask, at most the level's quota plus
-ties). GPU: svo_orb_detect is identical to the oracle -- same keypoints in the
+ties); the oracle's resize against an independent numpy restatement of
+INTER_LINEAR_EXACT at the level sizes of tests/orb_param_cases.py, whose cases are
+checked here to reach what they are there for. GPU: svo_orb_detect is identical to the oracle -- same keypoints in the
 same order with the same response and octave -- with and without masks, for
 Harris and FAST scoring, on the KITTI size and ragged sizes.
 """
@@ -40,6 +42,78 @@ def test_kat_resize_constant_and_ramp(dst):
     pos = np.clip((np.arange(dw) + 0.5) * (w / dw) - 0.5, 0, w - 1)
     assert np.abs(r[0] - pos).max() <= 0.5 + 1 / 256
     assert (np.diff(r[0]) >= 0).all()
+
+
+def _linear_exact_axis(ssize, dsize):
+    """INTER_LINEAR_EXACT along one axis, from OpenCV's description of it: sample
+    position f = scale (v + 0.5) - 0.5 with scale = 1 / (dsize / ssize) in double, taps
+    floor(f) and floor(f) + 1 with 8-bit fixed-point weights (round half to even),
+    the first / last sample at full weight where the taps leave the source."""
+    v = np.arange(dsize, dtype=np.float64)
+    scale = 1.0 / (np.float64(dsize) / np.float64(ssize))
+    f = scale * (v + 0.5) - 0.5
+    i = np.floor(f)
+    c1 = np.rint((f - i) * 256.0).astype(np.int64)
+    i = i.astype(np.int64)
+    first = (i < 0) | (ssize == 1)
+    last = ~first & (i >= ssize - 1)
+    i0 = np.where(first, 0, np.where(last, ssize - 1, i))
+    c1 = np.where(first | last, 0, c1)
+    i1 = np.minimum(i0 + 1, ssize - 1)  # (weight 0 wherever this clamps)
+    return i0, i1, 256 - c1, c1
+
+
+def _resize_linear_exact_np(a, dw, dh):
+    """The resize as one expression for every pixel, no separate path for clamped
+    rows or columns (oracle/orb.cpp rounds those from 8 fractional bits; the same
+    value algebraically, which the comparison pins)."""
+    a = a.astype(np.int64)
+    x0, x1, cx0, cx1 = _linear_exact_axis(a.shape[1], dw)
+    y0, y1, cy0, cy1 = _linear_exact_axis(a.shape[0], dh)
+    h0 = cx0 * a[y0][:, x0] + cx1 * a[y0][:, x1]
+    h1 = cx0 * a[y1][:, x0] + cx1 * a[y1][:, x1]
+    return ((cy0[:, None] * h0 + cy1[:, None] * h1 + 32768) >> 16).astype(np.uint8)
+
+
+def test_resize_restatement_matches_known_answers():
+    # the restatement itself: the half-size box mean, and a clamped single row / column
+    rng = np.random.default_rng(0)
+    a = rng.integers(0, 256, (30, 42), dtype=np.uint8)
+    s = a.reshape(15, 2, 21, 2).astype(int).sum(axis=(1, 3))
+    assert np.array_equal(_resize_linear_exact_np(a, 21, 15), (s + 2) >> 2)
+    assert np.array_equal(_resize_linear_exact_np(a[:1], 42, 3), np.repeat(a[:1], 3, 0))
+    assert np.array_equal(_resize_linear_exact_np(a[:, :1], 3, 30), np.repeat(a[:, :1], 3, 1))
+
+
+def _resize_pairs():
+    import orb_param_cases as P
+    return P.level_pairs() + [(1, 37, 1, 31), (1, 37, 1, 9), (53, 1, 44, 1), (53, 1, 17, 1), (5, 5, 1, 1)]
+
+
+def test_oracle_resize_matches_independent_restatement():
+    """O.resize_linear_exact (the reference of the GPU level tests) against the numpy
+    restatement above, at every pair of consecutive level sizes those tests use
+    (ratios 1.05 .. 3) and at one-pixel-wide, one-pixel-high and 1x1 images."""
+    pairs = _resize_pairs()
+    assert len(pairs) > 40
+    for k, (sw, sh, dw, dh) in enumerate(pairs):
+        rng = np.random.default_rng(100 + k)
+        for a in (rng.integers(0, 256, (sh, sw), dtype=np.uint8),
+                  rng.choice(np.array([0, 255], np.uint8), (sh, sw))):  # extremes: rounding at the ends of the range
+            got = O.resize_linear_exact(a, dw, dh)
+            assert np.array_equal(got, _resize_linear_exact_np(a, dw, dh)), f"{sw}x{sh} -> {dw}x{dh}"
+
+
+def test_orb_param_cases_reach_their_targets_on_the_oracle():
+    # (tests/test_orb_params_gpu.py asserts the same per case next to the GPU comparison)
+    import orb_param_cases as P
+    for cid in P.CASES:
+        P.check_reaches_target(cid)
+    assert P.level_info("base")[0].tolist() == [129, 107, 90, 75, 62, 52, 43, 36]
+    assert P.level_info("s2")[0].tolist() == [129, 64, 32]
+    assert P.level_info("s3")[0].tolist() == [200, 67, 22]
+    assert P.level_info("s15")[0].tolist() == [200, 133, 89, 59, 40]
+    assert (P.level_info("w257")[0][-1], P.level_info("w257")[1][-1]) == (72, 9)
 
 
 def test_kat_orb_level_schedule_kitti():
@@ -149,6 +223,25 @@ def test_gpu_orb_rejects_unsupported(ctx):
     p = S.OrbParams(nlevels=9)
     with pytest.raises(S.SvoError):
         ctx.orb_detect(g, p)
+    # Harris reads 4 px around a keypoint; a scale pyramid needs a factor > 1 and a level
+    for p in (S.OrbParams(edge_threshold=3), S.OrbParams(scale_factor=1.0), S.OrbParams(nlevels=0)):
+        with pytest.raises(S.SvoError):
+            ctx.orb_detect(g, p)
+        with pytest.raises(S.SvoError):
+            ctx.orb_level(g, p, None, 0)
+    # a level that rounds to 0 pixels: 2x2 at scale 2 is 2, 1, 0 (cvRound(0.5))
+    g2 = ctx.image(np.zeros((2, 2), np.uint8), max_levels=0)
+    p = S.OrbParams(scale_factor=2.0, nlevels=3, edge_threshold=4, patch_size=4)
+    with pytest.raises(S.SvoError):
+        ctx.orb_detect(g2, p)
+    with pytest.raises(S.SvoError):
+        ctx.orb_level(g2, p, None, 0)
+    # svo_orb_level: levels are 0 .. nlevels - 1
+    p = S.OrbParams(nlevels=3)
+    assert ctx.orb_level(g, p, None, 2)[0].shape == (44, 44)
+    for level in (3, -1):
+        with pytest.raises(S.SvoError):
+            ctx.orb_level(g, p, None, level)
 
 
 # ------------------------------------------------------------------ committed fixture
