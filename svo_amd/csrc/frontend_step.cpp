@@ -4,14 +4,14 @@
 //
 //   step(t), for every sequence s at once:
 //     pyramid + Scharr of left frame t+1, pyramid of right t   [pyramid.hip]   (beside LK)
-//     temporal LK  frame t-1 -> t (21x21, L3, 50 it)     [lk.hip]        trackFrames :154-179
+//     temporal LK  frame t-1 -> t (21x21, L3, 50 it)     [lk_multi.hip]  trackFrames :154-179
 //     mask of boxes around frame t-1's features + FAST   [fast.hip]      extractFeatures :74-92
 //     (host) final SQPnP fits of step t-1 -> poses       [pose.cpp]      calculatePose :191-214
 //     keyframe points of t-1 to the world frame, keep status == 1,
 //       gather map points, first RANSAC subsets          [fe_kernels]    :169-175, :182-187, :141
 //     RANSAC: host EPnP chunks <-> GPU scoring launches  [pose.cpp, pnp.hip] calculatePose :191-196
 //     drop outliers + the keyframe's first corners       [fe_kernels]    :218-229
-//     stereo LK of those corners into right frame t      [lk.hip]        findLeftFeaturesInRight :94-118
+//     stereo LK of those corners into right frame t      [lk_multi.hip]  findLeftFeaturesInRight :94-118
 //     |yR - yL| < 40, DLT triangulation, z > 0, append   [fe_kernels]    triangulateNewMapPoints :120-152
 //     (window enabled) the frame's lists into its ring slot [fe_kernels]  the back end's input, DESIGN.md §10
 //

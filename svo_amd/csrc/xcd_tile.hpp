@@ -40,8 +40,8 @@ __device__ __forceinline__ XcdTile xcd_tile() {
 // an XT template flag -- fast_detect_q_kernel<.., XT> (fast.hip) and
 // pyr_scharr_kernel<.., .., XT> (pyramid.hip). It does NOT switch the other
 // users of xcd_tile(), which always run in XCD order: fast_box_filter_kernel and
-// fast_emit_kernel (fast.hip), pyr_chain_kernel and its tail (pyramid.hip); LK
-// has its own switch (SVO_LK_XCD, lk.hip). The recorded A/B
+// fast_emit_kernel (fast.hip), pyr_chain_kernel and its tail (pyramid.hip), and
+// the four-features-per-wave LK kernels (lk_multi.hip, lk_cvq.hip). The recorded A/B
 // (profiles/r04/n_xcd_tiles_ab.txt) therefore measures those two kernels'
 // mapping only.
 inline bool xcd_tiles_on() {

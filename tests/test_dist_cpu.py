@@ -61,7 +61,13 @@ def test_bench_gpus_flag_launches_ranks():
     out = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--seq", "3", "--dry-run"],
                          env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
-    lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
+    # (the ranks share the pipe: two result lines can arrive as one, "{...}{...}")
+    dec, lines = json.JSONDecoder(), []
+    for x in out.stdout.splitlines():
+        while x.startswith("{"):
+            d, end = dec.raw_decode(x)
+            lines.append(d)
+            x = x[end:].lstrip()
     assert sorted(d["rank"] for d in lines) == [0, 1]
     assert all(d["world"] == 2 and d["total_sequences"] == 6 for d in lines)
     seeds = [s for d in lines for s in d["seeds"]]

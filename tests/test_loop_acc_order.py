@@ -5,7 +5,7 @@ Tracking mirror's default) sums the normal equations in OpenCV's own float
 SSE-lane order and equals the oracle's ACC_SSE bit for bit -- per call and
 through 200 frames of the loop, with no exemption (tests/test_lk_opencv_order_gpu.py).
 The batched benchmark front end's default sums exactly (integers, one rounding:
-lk.hip) and equals the oracle's ACC_EXACT bit for bit (the GPU suite). This file
+lk_multi.hip) and equals the oracle's ACC_EXACT bit for bit (the GPU suite). This file
 characterises only that second, documented choice: what exact sums instead of
 OpenCV's float order do to the reference's loop
 (R:src/tracking.cpp:154-179 trackFrames, :181-230 calculatePose) on the

@@ -115,7 +115,7 @@ def main():
         path = "/tmp/lk_mix_model.s"
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{REPO}/include",
                f"-I{REPO}/svo_amd/csrc", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-               f"{REPO}/svo_amd/csrc/lk.hip", "-o", path]
+               f"{REPO}/svo_amd/csrc/lk_multi.hip", "-o", path]
         subprocess.run(cmd, check=True)
     bl = blocks(kernel_asm(path, a.kernel))
     w_of = {0: 1.0, 1: a.levels, 2: a.iters}
