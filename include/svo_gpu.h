@@ -305,6 +305,39 @@ int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points,
                      const double K[9], double huber_delta, double lambda, double* U, double* gc, double* V,
                      double* gp, double* cost, double* S, double* b, double* dc, double* dp, int* n_free,
                      int* status);
+/* Stereo observations: svo_bundle_adjust / svo_ba_linearize with the right
+ * image's column per observation, obs_ur (P*max_obs floats), of a rectified pair
+ * whose right camera's centre lies at +baseline on the left camera's x axis.
+ * With P = R X + t an observation with obs_ur >= 0 has a third residual
+ *   r2 = fx (Px - baseline) / Pz + cx - obs_ur
+ * with the pose-Jacobian row (left perturbation, xr = (Px - baseline) / Pz)
+ *   [fx/Pz, 0, -fx xr/Pz, -fx xr y, fx (1 + xr x), -fx y]
+ * and the point-Jacobian row Jc[2, :3] R. In every sum its terms follow the two
+ * left rows' (U, gc, V, gp, W_ij stay 6x6, 6, 3x3, 3 and 6x3). The Huber weight and
+ * the cost take the norm of the residual the observation has: 3 components for
+ * a stereo observation, 2 for a monocular one. obs_ur < 0 marks a monocular
+ * observation (a measured column is never negative): it is evaluated exactly as
+ * by the monocular entries, so a call whose obs_ur are all negative returns their
+ * bits. The Pz <= 0 rule is unchanged (such an observation contributes nothing
+ * and counts nothing). A stereo observation in front of its camera counts as two
+ * views of its point: within a (point, camera) run of duplicates the count is
+ * one, plus one if any observation of the run is stereo, so a point with a single
+ * stereo observation is free. Every other rule above holds as it stands (positive
+ * definiteness, a free camera without observations, duplicates summed into one
+ * W_ij, fixed summation order). svo_bundle_adjust_stereo's scan for values that
+ * are not finite covers obs_ur within a problem's counts. SVO_ERR_ARG (nothing
+ * written) in addition: obs_ur NULL; baseline not finite or <= 0. */
+int svo_bundle_adjust_stereo(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs,
+                             const int* n_cams, const int* n_points, const int* n_obs, double* poses,
+                             const uint8_t* fixed, double* points, const int* obs_cam, const int* obs_point,
+                             const float* obs_xy, const float* obs_ur, double baseline, const double K[9],
+                             double huber_delta, int max_iterations, double* costs, int* iterations);
+int svo_ba_linearize_stereo(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs,
+                            const int* n_cams, const int* n_points, const int* n_obs, const double* poses,
+                            const uint8_t* fixed, const double* points, const int* obs_cam, const int* obs_point,
+                            const float* obs_xy, const float* obs_ur, double baseline, const double K[9],
+                            double huber_delta, double lambda, double* U, double* gc, double* V, double* gp,
+                            double* cost, double* S, double* b, double* dc, double* dp, int* n_free, int* status);
 /* The staging order of one problem's observations (host code, no GPU): the
  * stable sort by (point, camera). order[k] = index of the k-th staged
  * observation; pt_off (n_points + 1): point i owns staged positions
@@ -329,6 +362,13 @@ int svo_ba_sort_observations(const int* obs_cam, const int* obs_point, int n_obs
 int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
                        const float* xy, int* ocam, float* oxy, int* pt_off, int* cam_off, int* cam_idx, int* cam_pt,
                        int* pt_id, int* n_points, int* n_obs);
+/* svo_ba_stage_lists with the right column beside each pixel: ur (P*n_cams*cap,
+ * in the lists' order, < 0 = none) comes back as our (P*n_cams*cap, nullable) in
+ * staged order, as oxy does; everything else is svo_ba_stage_lists'. SVO_ERR_ARG
+ * in addition: ur NULL. */
+int svo_ba_stage_lists_stereo(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                              const float* xy, const float* ur, int* ocam, float* oxy, float* our, int* pt_off,
+                              int* cam_off, int* cam_idx, int* cam_pt, int* pt_id, int* n_points, int* n_obs);
 /* The device staging chain (svo_ba_stage_lists' kernels into a block sized from
  * the staged counts, as svo_frontend_bundle_adjust runs it) timed with HIP
  * events: reps runs after one warm-up, ms per chain (ms_device). Beside it what
@@ -529,6 +569,25 @@ int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* 
  * max_iterations < 0. */
 int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations, double* costs,
                                int* iterations, int* sizes);
+/* The stereo window: svo_frontend_window_enable, and the ring also keeps one
+ * float per feature and slot, the right image's column of the stereo match
+ * (findLeftFeaturesInRight's LK) that created the feature, in the frame that
+ * created it, and -1 in every later frame that tracks it; the init frame's
+ * features all carry theirs. With the plain svo_frontend_window_enable none of
+ * this is allocated or written. SVO_ERR_ARG in addition: the configuration's
+ * P_right gives no baseline -P_right[3] / P_right[0] > 0. */
+int svo_frontend_window_enable_stereo(svo_frontend* fe, int window);
+/* The right columns of sequence seq's valid slots in svo_frontend_window's order
+ * and with its cut: ur (W*cap). SVO_ERR_ARG: no stereo window enabled. */
+int svo_frontend_window_right(svo_frontend* fe, int seq, int cap, float* ur);
+/* svo_frontend_bundle_adjust with the stereo term (svo_bundle_adjust_stereo) on
+ * the ring's right columns, baseline = -P_right[3] / P_right[0] of the
+ * configuration: a point created at the newest frame, which one camera sees, is
+ * free. The results equal svo_bundle_adjust_stereo's, bit for bit, on the same
+ * window built on the host from svo_frontend_window and
+ * svo_frontend_window_right. SVO_ERR_ARG in addition: no stereo window enabled. */
+int svo_frontend_bundle_adjust_stereo(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations,
+                                      double* costs, int* iterations, int* sizes);
 /* Accumulated per-phase device time (ms) and launch counts since create/reset:
  * phases: 0 pyramid (left + Scharr), 1 lk, 2 post_lk, 3 stereo_lk, 4 pnp_score,
  * 5 tail (keyframe), 6 fast, 7 bucket, 8 append, 9 pyramid_right. Returns the number

@@ -132,6 +132,14 @@ _SIGS = [
     ("svo_ba_linearize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
                                    _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
                                    _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]),
+    ("svo_bundle_adjust_stereo", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p,
+                                           _f64p, _i32p, _i32p, _f32p, _f32p, C.c_double, _f64p, C.c_double, C.c_int,
+                                           _f64p, _i32p]),
+    ("svo_ba_linearize_stereo", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p,
+                                          _f64p, _i32p, _i32p, _f32p, _f32p, C.c_double, _f64p, C.c_double, C.c_double,
+                                          _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]),
+    ("svo_ba_stage_lists_stereo", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, _i32p, _f32p,
+                                            _f32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     ("svo_ba_sort_observations", C.c_int, [_i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p]),
     ("svo_ba_stage_lists", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _i32p, _f32p, _i32p, _i32p,
                                      _i32p, _i32p, _i32p, _i32p, _i32p]),
@@ -147,6 +155,9 @@ _SIGS = [
     ("svo_frontend_window_enable", C.c_int, [_vp, C.c_int]),
     ("svo_frontend_window", C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _f64p, _i32p, _i32p, _f32p]),
     ("svo_frontend_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
+    ("svo_frontend_window_enable_stereo", C.c_int, [_vp, C.c_int]),
+    ("svo_frontend_window_right", C.c_int, [_vp, C.c_int, C.c_int, _f32p]),
+    ("svo_frontend_bundle_adjust_stereo", C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
     ("svo_frontend_time_pyramid", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_time_fast", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_pyramid_level", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
@@ -614,31 +625,45 @@ class Context:
         cnt = [None if c is None else _c(np.asarray(c).reshape(P), np.int32) for c in (n_cams, n_points, n_obs)]
         return single, P, Cn, Mn, On, poses, fixed, points, obs_cam, obs_point, obs_xy, K, cnt
 
+    @staticmethod
+    def _ba_stereo(obs_ur, baseline, P, On):
+        """The stereo entries' two extra arguments, or None when neither is given."""
+        if obs_ur is None and baseline is None:
+            return None
+        if obs_ur is None or baseline is None:
+            raise ValueError("obs_ur and baseline go together")
+        return [_p(_c(np.asarray(obs_ur).reshape(P, On), np.float32), _f32p), float(baseline)]
+
     def bundle_adjust(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams=None, n_points=None,
-                      n_obs=None, huber_delta: float = 0.0, max_iterations: int = 50):
+                      n_obs=None, huber_delta: float = 0.0, max_iterations: int = 50, obs_ur=None, baseline=None):
         """Windowed bundle adjustment (svo_bundle_adjust): poses (P, C, 12) world ->
         camera, fixed (P, C) bool, points (P, M, 3), observations obs_cam / obs_point
         (P, O) and obs_xy (P, O, 2) in any order; n_cams / n_points / n_obs: (P,)
         counts of a ragged batch. One problem may be given without the leading axis.
+        obs_ur (P, O) with baseline: the right image's column per observation (< 0:
+        a monocular observation) of a rectified pair (svo_bundle_adjust_stereo).
         -> (poses, points, costs (P, 2): initial and final, iterations (P,))."""
         single, P, Cn, Mn, On, poses, fixed, points, oc, op, oxy, K, cnt = self._ba_args(
             poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs)
         costs = np.zeros((P, 2), np.float64)
         its = np.zeros(P, np.int32)
-        self._check(lib().svo_bundle_adjust(
+        stereo = self._ba_stereo(obs_ur, baseline, P, On)
+        entry = lib().svo_bundle_adjust if stereo is None else lib().svo_bundle_adjust_stereo
+        self._check(entry(
             self.handle, P, Cn, Mn, On, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
-            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), _p(K, _f64p),
-            float(huber_delta), int(max_iterations), _p(costs, _f64p), _p(its, _i32p)))
+            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), *(stereo or []),
+            _p(K, _f64p), float(huber_delta), int(max_iterations), _p(costs, _f64p), _p(its, _i32p)))
         if single:
             return poses[0], points[0], costs[0], int(its[0])
         return poses, points, costs, its
 
     def ba_linearize(self, poses, fixed, points, obs_cam, obs_point, obs_xy, K, lam: float = 1e-4, n_cams=None,
-                     n_points=None, n_obs=None, huber_delta: float = 0.0) -> dict:
+                     n_points=None, n_obs=None, huber_delta: float = 0.0, obs_ur=None, baseline=None) -> dict:
         """One linearisation and one solve of the bundle adjustment at damping lam
         (svo_ba_linearize) -> dict of U (P, C, 21), gc (P, C, 6), V (P, M, 6), gp
         (P, M, 3), cost (P,), S (P, 6C, 6C), b (P, 6C), dc (P, C, 6), dp (P, M, 3),
-        n_free (P,), status (P,); without the leading axis for one problem."""
+        n_free (P,), status (P,); without the leading axis for one problem. obs_ur
+        with baseline: svo_ba_linearize_stereo."""
         single, P, Cn, Mn, On, poses, fixed, points, oc, op, oxy, K, cnt = self._ba_args(
             poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs)
         out = {"U": np.zeros((P, Cn, 21)), "gc": np.zeros((P, Cn, 6)), "V": np.zeros((P, Mn, 6)),
@@ -646,21 +671,24 @@ class Context:
                "b": np.zeros((P, 6 * Cn)), "dc": np.zeros((P, Cn, 6)), "dp": np.zeros((P, Mn, 3))}
         nfree = np.zeros(P, np.int32)
         status = np.zeros(P, np.int32)
-        self._check(lib().svo_ba_linearize(
+        stereo = self._ba_stereo(obs_ur, baseline, P, On)
+        entry = lib().svo_ba_linearize if stereo is None else lib().svo_ba_linearize_stereo
+        self._check(entry(
             self.handle, P, Cn, Mn, On, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
-            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), _p(K, _f64p),
-            float(huber_delta), float(lam), *[_p(out[k], _f64p) for k in ("U", "gc", "V", "gp", "cost", "S", "b",
-                                                                          "dc", "dp")],
+            _p(fixed, _u8p), _p(points, _f64p), _p(oc, _i32p), _p(op, _i32p), _p(oxy, _f32p), *(stereo or []),
+            _p(K, _f64p), float(huber_delta), float(lam),
+            *[_p(out[k], _f64p) for k in ("U", "gc", "V", "gp", "cost", "S", "b", "dc", "dp")],
             _p(nfree, _i32p), _p(status, _i32p)))
         out["n_free"], out["status"] = nfree, status
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def ba_stage_lists(self, counts, ids, xy) -> dict:
+    def ba_stage_lists(self, counts, ids, xy, ur=None) -> dict:
         """The bundle adjustment's staging on the device (svo_ba_stage_lists) of
         observations given as sorted lists per camera: counts (P, W), ids (P, W, cap)
         strictly increasing per list, xy (P, W, cap, 2) -> dict of ocam (P, O), oxy
         (P, O, 2), pt_off (P, O + 1), cam_off (P, W + 1), cam_idx, cam_pt, pt_id
-        (P, O), n_points, n_obs (P,), O = W * cap."""
+        (P, O), n_points, n_obs (P,), O = W * cap. ur (P, W, cap): the right columns
+        beside xy, staged as "our" (P, O) (svo_ba_stage_lists_stereo)."""
         counts = _c(counts, np.int32)
         P, W = counts.shape
         ids = _c(ids, np.int32).reshape(P, W, -1)
@@ -671,6 +699,14 @@ class Context:
                "pt_off": np.zeros((P, O + 1), np.int32), "cam_off": np.zeros((P, W + 1), np.int32),
                "cam_idx": np.zeros((P, O), np.int32), "cam_pt": np.zeros((P, O), np.int32),
                "pt_id": np.zeros((P, O), np.int32), "n_points": np.zeros(P, np.int32), "n_obs": np.zeros(P, np.int32)}
+        if ur is not None:
+            ur = _c(ur, np.float32).reshape(P, W, cap)
+            out["our"] = np.zeros((P, O), np.float32)
+            self._check(lib().svo_ba_stage_lists_stereo(
+                self.handle, P, W, cap, _p(counts, _i32p), _p(ids, _i32p), _p(xy, _f32p), _p(ur, _f32p),
+                _p(out["ocam"], _i32p), _p(out["oxy"], _f32p), _p(out["our"], _f32p),
+                *[_p(out[k], _i32p) for k in ("pt_off", "cam_off", "cam_idx", "cam_pt", "pt_id", "n_points", "n_obs")]))
+            return out
         self._check(lib().svo_ba_stage_lists(
             self.handle, P, W, cap, _p(counts, _i32p), _p(ids, _i32p), _p(xy, _f32p), _p(out["ocam"], _i32p),
             _p(out["oxy"], _f32p), *[_p(out[k], _i32p) for k in ("pt_off", "cam_off", "cam_idx", "cam_pt", "pt_id",
@@ -884,16 +920,22 @@ class Frontend:
         self.ctx._check(lib().svo_frontend_map_points(self.handle, seq, _p(xyz, _f64p), cap, C.byref(n)))
         return xyz[: min(n.value, cap)].copy()
 
-    def window_enable(self, window):
+    def window_enable(self, window, stereo=False):
         """Keep the last `window` (1 .. BA_MAX_CAMS) frames' observations per sequence
-        on the device (svo_frontend_window_enable); once, before init."""
-        self.ctx._check(lib().svo_frontend_window_enable(self.handle, int(window)))
+        on the device (svo_frontend_window_enable); once, before init. stereo: also
+        the right column of the match that created each feature
+        (svo_frontend_window_enable_stereo)."""
+        enable = lib().svo_frontend_window_enable_stereo if stereo else lib().svo_frontend_window_enable
+        self.ctx._check(enable(self.handle, int(window)))
         self._window = int(window)
+        self._window_stereo = bool(stereo)
 
     def window(self, seq):
         """The valid frames of sequence seq's window, oldest first (svo_frontend_window)
         -> dict of frame_t (n,), poses (n, 12) world -> camera, ids and xy: lists of n
-        arrays (k,) int32 map ids / (k, 2) float32 pixels."""
+        arrays (k,) int32 map ids / (k, 2) float32 pixels; with a stereo window also
+        ur: n arrays (k,) float32, the right column in the frame that created the
+        feature and -1 in the frames that tracked it (svo_frontend_window_right)."""
         W = getattr(self, "_window", 0) or 1
         cap = (self.cfg.n_features + 63) // 64 * 64
         n = C.c_int()
@@ -904,21 +946,34 @@ class Frontend:
         self.ctx._check(lib().svo_frontend_window(self.handle, int(seq), cap, C.byref(n), _p(ft, _i32p),
                                                   _p(poses, _f64p), _p(cnt, _i32p), _p(ids, _i32p), _p(xy, _f32p)))
         k = n.value
-        return {"frame_t": ft[:k].copy(), "poses": poses[:k].copy(),
-                "ids": [ids[j, :cnt[j]].copy() for j in range(k)], "xy": [xy[j, :cnt[j]].copy() for j in range(k)]}
+        out = {"frame_t": ft[:k].copy(), "poses": poses[:k].copy(),
+               "ids": [ids[j, :cnt[j]].copy() for j in range(k)], "xy": [xy[j, :cnt[j]].copy() for j in range(k)]}
+        if getattr(self, "_window_stereo", False):
+            out["ur"] = [u[:c].copy() for u, c in zip(self.window_right(seq), cnt[:k])]
+        return out
 
-    def bundle_adjust(self, n_fixed=2, huber_delta=0.0, max_iterations=10):
+    def window_right(self, seq):
+        """(W, cap) float32: the right columns of sequence seq's window in window()'s
+        order (svo_frontend_window_right); an error without a stereo window."""
+        W = getattr(self, "_window", 0) or 1
+        cap = (self.cfg.n_features + 63) // 64 * 64
+        ur = np.zeros((W, cap), np.float32)
+        self.ctx._check(lib().svo_frontend_window_right(self.handle, int(seq), cap, _p(ur, _f32p)))
+        return ur
+
+    def bundle_adjust(self, n_fixed=2, huber_delta=0.0, max_iterations=10, stereo=False):
         """Windowed bundle adjustment of every sequence from its own window, on the
         device (svo_frontend_bundle_adjust): refined points into the map, refined
         poses into the window -> (costs (S, 2): initial and final, iterations (S,),
-        sizes (S, 3): frames, points, observations)."""
+        sizes (S, 3): frames, points, observations). stereo: with the right columns
+        of a stereo window and the rig's baseline (svo_frontend_bundle_adjust_stereo)."""
         S = self.cfg.n_seq
         costs = np.zeros((S, 2), np.float64)
         its = np.zeros(S, np.int32)
         sizes = np.zeros((S, 3), np.int32)
-        self.ctx._check(lib().svo_frontend_bundle_adjust(self.handle, int(n_fixed), float(huber_delta),
-                                                         int(max_iterations), _p(costs, _f64p), _p(its, _i32p),
-                                                         _p(sizes, _i32p)))
+        adjust = lib().svo_frontend_bundle_adjust_stereo if stereo else lib().svo_frontend_bundle_adjust
+        self.ctx._check(adjust(self.handle, int(n_fixed), float(huber_delta), int(max_iterations), _p(costs, _f64p),
+                               _p(its, _i32p), _p(sizes, _i32p)))
         return costs, its, sizes
 
     def time_pyramid(self, t, reps=20):

@@ -18,6 +18,12 @@
 // seen by fewer than two cameras in front of them, and points whose damped block
 // is not positive definite, are held constant; a free camera with no observation
 // in front of it is treated as fixed.
+// Stereo (kStereo, the batch's `our` plane; DESIGN.md section 10, "Stereo observations"): an
+// observation whose right column ur is >= 0 has a third residual row, on the
+// rectified right camera at +baseline on the left camera's x axis, added behind
+// the two left rows in every sum; it weighs and costs by its 3-norm and counts
+// as two views of its point. An observation with ur < 0 has a zero third row and
+// so the monocular bits. The monocular instantiations are the code as it was.
 #include "ba.hpp"
 
 namespace svo {
@@ -45,18 +51,24 @@ __device__ __forceinline__ int wave_sum_int(int v) {
 }
 
 struct Cam {
-    double fx, fy, cx, cy, delta;
+    double fx, fy, cx, cy, delta, bl;
 };
 
-// reproj_kernel's residual, Jacobian, weight and cost; false (nothing written)
-// when the point is not in front of the camera
-__device__ __forceinline__ bool obs_eval(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
-                                         const float* __restrict__ u, double& r0, double& r1, double& w, double& cost,
-                                         double J[12]) {
+template <bool kStereo>
+constexpr int kRows = kStereo ? 3 : 2;
+
+// reproj_kernel's residual, Jacobian, weight and cost; 0 (nothing written) when
+// the point is not in front of the camera, else 1, or 2 for a stereo observation
+// (*ur >= 0): r[2] and row 2 of J are the right column's, zero for a monocular one
+template <bool kStereo>
+__device__ __forceinline__ int obs_eval(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
+                                        const float* __restrict__ u, const float* __restrict__ ur,
+                                        double& r0, double& r1, double& r2, double& w, double& cost,
+                                        double J[6 * kRows<kStereo>]) {
     const double px = T[0] * X[0] + T[1] * X[1] + T[2] * X[2] + T[9];
     const double py = T[3] * X[0] + T[4] * X[1] + T[5] * X[2] + T[10];
     const double pz = T[6] * X[0] + T[7] * X[1] + T[8] * X[2] + T[11];
-    if (!(pz > 0)) return false;
+    if (!(pz > 0)) return 0;
     const double iz = 1.0 / pz, x = px * iz, y = py * iz;
     r0 = k.fx * x + k.cx - (double)u[0];
     r1 = k.fy * y + k.cy - (double)u[1];
@@ -72,32 +84,64 @@ __device__ __forceinline__ bool obs_eval(const Cam& k, const double* __restrict_
     J[9] = -k.fy * (1 + y * y);
     J[10] = k.fy * x * y;
     J[11] = k.fy * x;
-    const double nr = sqrt(r0 * r0 + r1 * r1);
-    const bool robust = k.delta > 0 && nr > k.delta;
-    w = robust ? k.delta / nr : 1.0;
-    cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * (r0 * r0 + r1 * r1);
-    return true;
+    if constexpr (!kStereo) {
+        const double nr = sqrt(r0 * r0 + r1 * r1);
+        const bool robust = k.delta > 0 && nr > k.delta;
+        w = robust ? k.delta / nr : 1.0;
+        cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * (r0 * r0 + r1 * r1);
+        return 1;
+    } else {
+        const float urv = *ur;
+        const bool st = urv >= 0.f;
+        const double xr = (px - k.bl) * iz;
+        r2 = st ? k.fx * xr + k.cx - (double)urv : 0.0;
+        J[12] = st ? k.fx * iz : 0.0;
+        J[13] = 0;
+        J[14] = st ? -k.fx * xr * iz : 0.0;
+        J[15] = st ? -k.fx * xr * y : 0.0;
+        J[16] = st ? k.fx * (1 + xr * x) : 0.0;
+        J[17] = st ? -k.fx * y : 0.0;
+        const double n2 = (r0 * r0 + r1 * r1) + r2 * r2;
+        const double nr = sqrt(n2);
+        const bool robust = k.delta > 0 && nr > k.delta;
+        w = robust ? k.delta / nr : 1.0;
+        cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * n2;
+        return st ? 2 : 1;
+    }
 }
 
 // Jp = Jc[:, :3] R (row a of Jp at Jp[3 a])
-__device__ __forceinline__ void point_jacobian(const double J[12], const double* __restrict__ T, double Jp[6]) {
+template <bool kStereo>
+__device__ __forceinline__ void point_jacobian(const double J[6 * kRows<kStereo>], const double* __restrict__ T,
+                                               double Jp[3 * kRows<kStereo>]) {
 #pragma unroll
-    for (int a = 0; a < 2; a++)
+    for (int a = 0; a < kRows<kStereo>; a++)
 #pragma unroll
         for (int c = 0; c < 3; c++) Jp[3 * a + c] = J[6 * a] * T[c] + J[6 * a + 1] * T[3 + c] + J[6 * a + 2] * T[6 + c];
+}
+
+// w (a0 b0 + a1 b1), and behind them the stereo row's a2 b2 (never read in the
+// monocular instantiation, where the row does not exist)
+template <bool kStereo>
+__device__ __forceinline__ double rows_dot(double w, double a0, double b0, double a1, double b1, const double* a2,
+                                           const double* b2) {
+    if constexpr (kStereo)
+        return w * ((a0 * b0 + a1 * b1) + *a2 * *b2);
+    else
+        return w * (a0 * b0 + a1 * b1);
 }
 
 // ------------------------------------------------------------------ stage 1 / 5: per camera
 // One block per (camera, problem); thread t takes the camera's observations
 // t, t + 256, ... in order. kFull: U, gc, cost and the in-front count; else the
 // cost alone.
-template <bool kFull>
+template <bool kFull, bool kStereo>
 __global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double* __restrict__ poses,
                                                         const double* __restrict__ points) {
     constexpr int kN = kFull ? kBaNE : 1;
     const int p = blockIdx.y, j = blockIdx.x;
     if (!d.active[p] || j >= d.n_cams[p]) return;
-    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta, d.baseline};
     const double* T = poses + 12 * ((size_t)p * d.maxC + j);
     const size_t ob = (size_t)p * d.maxO;
     const int o0 = d.cam_off[(size_t)p * (d.maxC + 1) + j], o1 = d.cam_off[(size_t)p * (d.maxC + 1) + j + 1];
@@ -108,17 +152,20 @@ __global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double*
     for (int a = o0 + (int)threadIdx.x; a < o1; a += 256) {
         const int o = d.cam_idx[ob + a];
         const double* X = points + 3 * ((size_t)p * d.maxM + d.cam_pt[ob + a]);
-        double r0, r1, w, c, J[12];
-        if (!obs_eval(k, T, X, d.oxy + 2 * (ob + o), r0, r1, w, c, J)) continue;
+        double r0, r1, r2, w, c, J[6 * kRows<kStereo>];
+        const float* ur = kStereo ? d.our + (ob + o) : nullptr;
+        if (!obs_eval<kStereo>(k, T, X, d.oxy + 2 * (ob + o), ur, r0, r1, r2, w, c, J)) continue;
         cnt++;
         if (kFull) {
             int q = 0;
 #pragma unroll
             for (int a2 = 0; a2 < 6; a2++)
 #pragma unroll
-                for (int c2 = a2; c2 < 6; c2++) e[q++] += w * (J[a2] * J[c2] + J[6 + a2] * J[6 + c2]);
+                for (int c2 = a2; c2 < 6; c2++)
+                    e[q++] += rows_dot<kStereo>(w, J[a2], J[c2], J[6 + a2], J[6 + c2], J + 12 + a2, J + 12 + c2);
 #pragma unroll
-            for (int a2 = 0; a2 < 6; a2++) e[21 + a2] += w * (J[a2] * r0 + J[6 + a2] * r1);
+            for (int a2 = 0; a2 < 6; a2++)
+                e[21 + a2] += rows_dot<kStereo>(w, J[a2], r0, J[6 + a2], r1, J + 12 + a2, &r2);
         }
         e[kN - 1] += c;
     }
@@ -158,31 +205,41 @@ __global__ void ba_cost_sum_kernel(BaBatch d, const double* __restrict__ src, in
 // ------------------------------------------------------------------ stage 1 / 2: per point
 // One thread per point: V, gp over its observations in camera order, then the
 // damped block's inverse by cofactors.
+template <bool kStereo>
 __global__ __launch_bounds__(256) void ba_point_kernel(BaBatch d, const double* __restrict__ poses,
                                                        const double* __restrict__ points) {
     const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (!d.active[p] || i >= d.n_points[p]) return;
-    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta, d.baseline};
     const size_t ob = (size_t)p * d.maxO, pi = (size_t)p * d.maxM + i;
     const double* X = points + 3 * pi;
     const int o0 = d.pt_off[(size_t)p * (d.maxM + 1) + i], o1 = d.pt_off[(size_t)p * (d.maxM + 1) + i + 1];
     double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
     int nfront = 0, prev = -1;  // distinct cameras in front: a camera's observations are consecutive
+    bool two = false;           // the current camera's run already counts its stereo view
     for (int a = o0; a < o1; a++) {
         const int cam = d.ocam[ob + a];
         const double* T = poses + 12 * ((size_t)p * d.maxC + cam);
-        double r0, r1, w, c, J[12], Jp[6];
-        if (!obs_eval(k, T, X, d.oxy + 2 * (ob + a), r0, r1, w, c, J)) continue;
+        double r0, r1, r2, w, c, J[6 * kRows<kStereo>], Jp[3 * kRows<kStereo>];
+        const int kind =
+            obs_eval<kStereo>(k, T, X, d.oxy + 2 * (ob + a), kStereo ? d.our + (ob + a) : nullptr, r0, r1, r2, w, c, J);
+        if (!kind) continue;
         nfront += cam != prev;
+        if constexpr (kStereo) {
+            two = two && cam == prev;
+            nfront += kind == 2 && !two;
+            two = two || kind == 2;
+        }
         prev = cam;
-        point_jacobian(J, T, Jp);
+        point_jacobian<kStereo>(J, T, Jp);
         int q = 0;
 #pragma unroll
         for (int s = 0; s < 3; s++)
 #pragma unroll
-            for (int t = s; t < 3; t++) V[q++] += w * (Jp[s] * Jp[t] + Jp[3 + s] * Jp[3 + t]);
+            for (int t = s; t < 3; t++)
+                V[q++] += rows_dot<kStereo>(w, Jp[s], Jp[t], Jp[3 + s], Jp[3 + t], Jp + 6 + s, Jp + 6 + t);
 #pragma unroll
-        for (int s = 0; s < 3; s++) g[s] += w * (Jp[s] * r0 + Jp[3 + s] * r1);
+        for (int s = 0; s < 3; s++) g[s] += rows_dot<kStereo>(w, Jp[s], r0, Jp[3 + s], r1, Jp + 6 + s, &r2);
     }
 #pragma unroll
     for (int q = 0; q < 6; q++) d.pt_V[6 * pi + q] = V[q];
@@ -205,15 +262,17 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BaBatch d, const double* 
 }
 
 // W_ij = sum over point i's observations by camera `cam` of w Jc^T Jp (6x3, row-major)
+template <bool kStereo>
 __device__ __forceinline__ void accumulate_W(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
-                                             const float* __restrict__ u, double W[18]) {
-    double r0, r1, w, c, J[12], Jp[6];
-    if (!obs_eval(k, T, X, u, r0, r1, w, c, J)) return;
-    point_jacobian(J, T, Jp);
+                                             const float* __restrict__ u, const float* __restrict__ ur, double W[18]) {
+    double r0, r1, r2, w, c, J[6 * kRows<kStereo>], Jp[3 * kRows<kStereo>];
+    if (!obs_eval<kStereo>(k, T, X, u, ur, r0, r1, r2, w, c, J)) return;
+    point_jacobian<kStereo>(J, T, Jp);
 #pragma unroll
     for (int x = 0; x < 6; x++)
 #pragma unroll
-        for (int t = 0; t < 3; t++) W[3 * x + t] += w * (J[x] * Jp[t] + J[6 + x] * Jp[3 + t]);
+        for (int t = 0; t < 3; t++)
+            W[3 * x + t] += rows_dot<kStereo>(w, J[x], Jp[t], J[6 + x], Jp[3 + t], J + 12 + x, Jp + 6 + t);
 }
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
@@ -225,6 +284,7 @@ __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 // camera does not see the point or the point is constant), then every thread
 // subtracts Y_ij W_ik^T from its entries, points in index order. The assembled
 // system is factored and solved in LDS.
+template <bool kStereo>
 __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d, const double* __restrict__ poses,
                                                                        const double* __restrict__ points,
                                                                        double* __restrict__ S_out,
@@ -238,7 +298,7 @@ __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d
     __shared__ int freecam[kMaxCams], camslot[kMaxCams];  // free index -> camera and back (-1: not free)
     __shared__ int soff[kPT + 1], slive[kPT];
     __shared__ int s_nfree;
-    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta, d.baseline};
     const int C = d.n_cams[p], M = d.n_points[p];
     const size_t cb = (size_t)p * d.maxC, ob = (size_t)p * d.maxO, pb = (size_t)p * d.maxM;
     if (t == 0) {
@@ -313,7 +373,7 @@ __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d
 #pragma unroll
             for (int z = 0; z < 18; z++) W[z] = 0;
             for (int a2 = a; a2 < soff[q + 1] && d.ocam[ob + a2] == cam; a2++)
-                accumulate_W(k, T, X, d.oxy + 2 * (ob + a2), W);
+                accumulate_W<kStereo>(k, T, X, d.oxy + 2 * (ob + a2), kStereo ? d.our + (ob + a2) : nullptr, W);
             const double* Vi = d.pt_Vinv + 6 * (pb + i);
             const double v00 = Vi[0], v01 = Vi[1], v02 = Vi[2], v11 = Vi[3], v12 = Vi[4], v22 = Vi[5];
             double* Wo = Wl + q * kWStride + jf * 18;
@@ -409,13 +469,14 @@ __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d
 }
 
 // ------------------------------------------------------------------ stage 4: points
+template <bool kStereo>
 __global__ __launch_bounds__(256) void ba_point_update_kernel(BaBatch d, const double* __restrict__ poses,
                                                               const double* __restrict__ points,
                                                               double* __restrict__ trial_points,
                                                               double* __restrict__ dp_out) {
     const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (!d.active[p]) return;
-    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta};
+    const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta, d.baseline};
     const size_t cb = (size_t)p * d.maxC, ob = (size_t)p * d.maxO, pi = (size_t)p * d.maxM + i;
     double sd = 0, sx = 0;
     if (i < d.n_points[p]) {
@@ -431,7 +492,8 @@ __global__ __launch_bounds__(256) void ba_point_update_kernel(BaBatch d, const d
                 double W[18];
 #pragma unroll
                 for (int z = 0; z < 18; z++) W[z] = 0;
-                accumulate_W(k, poses + 12 * (cb + cam), X, d.oxy + 2 * (ob + a), W);
+                accumulate_W<kStereo>(k, poses + 12 * (cb + cam), X, d.oxy + 2 * (ob + a),
+                                      kStereo ? d.our + (ob + a) : nullptr, W);
                 const double* dc = d.dc + 6 * (cb + cam);
 #pragma unroll
                 for (int s = 0; s < 3; s++)
@@ -567,17 +629,31 @@ int ba_point_blocks(int max_points) { return max_points > 0 ? (max_points + 255)
 
 hipError_t launch_ba_linearize(const BaBatch& b, const double* poses, const double* points, hipStream_t st) {
     if (b.P <= 0) return hipSuccess;
-    if (b.maxC > 0)
-        hipLaunchKernelGGL(ba_camera_kernel<true>, dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
-    if (b.maxM > 0)
-        hipLaunchKernelGGL(ba_point_kernel, dim3((b.maxM + 255) / 256, b.P), dim3(256), 0, st, b, poses, points);
+    if (b.maxC > 0) {
+        if (b.our)
+            hipLaunchKernelGGL((ba_camera_kernel<true, true>), dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+        else
+            hipLaunchKernelGGL((ba_camera_kernel<true, false>), dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+    }
+    if (b.maxM > 0) {
+        const dim3 grid((b.maxM + 255) / 256, b.P);
+        if (b.our)
+            hipLaunchKernelGGL(ba_point_kernel<true>, grid, dim3(256), 0, st, b, poses, points);
+        else
+            hipLaunchKernelGGL(ba_point_kernel<false>, grid, dim3(256), 0, st, b, poses, points);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_ba_schur_solve(const BaBatch& b, const double* poses, const double* points, double* S_out,
                                  double* b_out, hipStream_t st) {
     if (b.P <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ba_schur_solve_kernel, dim3(b.P), dim3(kSolveThreads), 0, st, b, poses, points, S_out, b_out);
+    if (b.our)
+        hipLaunchKernelGGL(ba_schur_solve_kernel<true>, dim3(b.P), dim3(kSolveThreads), 0, st, b, poses, points, S_out,
+                           b_out);
+    else
+        hipLaunchKernelGGL(ba_schur_solve_kernel<false>, dim3(b.P), dim3(kSolveThreads), 0, st, b, poses, points, S_out,
+                           b_out);
     return hipGetLastError();
 }
 
@@ -585,16 +661,24 @@ hipError_t launch_ba_update(const BaBatch& b, const double* poses, const double*
                             double* trial_points, double* dp_out, hipStream_t st) {
     if (b.P <= 0) return hipSuccess;
     const int nblk = ba_point_blocks(b.maxM);
-    hipLaunchKernelGGL(ba_point_update_kernel, dim3(nblk, b.P), dim3(256), 0, st, b, poses, points, trial_points,
-                       dp_out);
+    if (b.our)
+        hipLaunchKernelGGL(ba_point_update_kernel<true>, dim3(nblk, b.P), dim3(256), 0, st, b, poses, points,
+                           trial_points, dp_out);
+    else
+        hipLaunchKernelGGL(ba_point_update_kernel<false>, dim3(nblk, b.P), dim3(256), 0, st, b, poses, points,
+                           trial_points, dp_out);
     hipLaunchKernelGGL(ba_pose_update_kernel, dim3(b.P), dim3(64), 0, st, b, poses, trial_poses, nblk);
     return hipGetLastError();
 }
 
 hipError_t launch_ba_cost(const BaBatch& b, const double* poses, const double* points, double* cost, hipStream_t st) {
     if (b.P <= 0) return hipSuccess;
-    if (b.maxC > 0)
-        hipLaunchKernelGGL(ba_camera_kernel<false>, dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+    if (b.maxC > 0) {
+        if (b.our)
+            hipLaunchKernelGGL((ba_camera_kernel<false, true>), dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+        else
+            hipLaunchKernelGGL((ba_camera_kernel<false, false>), dim3(b.maxC, b.P), dim3(256), 0, st, b, poses, points);
+    }
     hipLaunchKernelGGL(ba_cost_sum_kernel, dim3((b.P + 255) / 256), dim3(256), 0, st, b, b.cam_cost, 1, 0, cost);
     return hipGetLastError();
 }

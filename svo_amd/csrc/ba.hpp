@@ -41,6 +41,9 @@ struct BaBatch {
     double* step_part; // [P][point blocks][2]: |dp|^2, |X|^2 of the free points
     double* stepinfo;  // [P][2]: |step|^2, |free state|^2
     double* cam_cost;  // [P][maxC]: cost-only pass
+    // stereo (nullable: null runs the monocular kernels)
+    const float* our;  // [P][maxO]: the right image's column, < 0 = monocular observation
+    double baseline;   // > 0: the right camera's centre on the left camera's x axis
 };
 
 int ba_point_blocks(int max_points);
@@ -72,6 +75,7 @@ struct BaLists {
     const int* counts;  // [P][W], by camera
     const int* ids;     // [P][W][cap], by list
     const float* xy;    // [P][W][cap][2], by list
+    const float* ur = nullptr;  // [P][W][cap], by list: the right column (< 0: none); nullable
 };
 // the chain's own memory, sized for W cap observations per problem (12 bytes each)
 struct BaStageWork {
@@ -91,6 +95,7 @@ struct BaStageOut {
     double* points;
     const double* map;
     int map_cap;
+    float* our = nullptr;  // written where the lists carry ur and this is not null
 };
 int ba_stage_blocks(int W, int cap);
 size_t ba_stage_work_bytes(int P, int W, int cap);
@@ -122,6 +127,7 @@ struct BaDeviceWindow {
     double* map;        // [P][map_cap][3]
     int map_cap;
     int n_fixed;
+    double baseline = 0;  // > 0 with lists.ur: the stereo term
 };
 int ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[9], double huber_delta,
                      int max_iterations, double* costs, int* iterations, int* sizes);

@@ -120,6 +120,7 @@ __global__ __launch_bounds__(kPlaceBlock) void ba_stage_fill_kernel(BaLists L, B
     O.ocam[dst] = j;
     O.oxy[2 * dst] = L.xy[2 * src];
     O.oxy[2 * dst + 1] = L.xy[2 * src + 1];
+    if (L.ur && O.our) O.our[dst] = L.ur[src];
     O.cam_idx[(size_t)p * O.maxO + off[j] + k] = pos;
     Wk.flag[(size_t)p * WC + pos] = (int)(v >> 31);
     Wk.smid[(size_t)p * WC + pos] = L.ids[src];

@@ -48,7 +48,16 @@ struct Args {
     const float* obs_xy;
     const double* K;
     double delta;
+    const float* obs_ur = nullptr;  // stereo: the right column per observation (< 0: monocular) ...
+    double baseline = 0;            // ... and the rig's baseline; null / 0 for the monocular entries
 };
+
+// the stereo entries' own two arguments
+const char* check_stereo(const float* obs_ur, double baseline) {
+    if (!obs_ur) return "obs_ur is null";
+    if (!std::isfinite(baseline) || !(baseline > 0)) return "baseline is not a finite length > 0";
+    return nullptr;
+}
 
 const char* check(const Args& a) {
     if (a.P < 0 || a.maxC < 0 || a.maxM < 0 || a.maxO < 0) return "negative size";
@@ -80,12 +89,13 @@ struct Staged {
     int nblk;
     // the staged problem (what b's const pointers name), for whoever fills it
     int *n_cams, *n_points, *ocam, *cam_idx, *cam_pt, *pt_off, *cam_off, *pt_id;
-    float* oxy;
+    float *oxy, *our;  // our: null for a monocular batch
     uint8_t* fixed;
 };
 
 struct Sizes {
     int P, maxC, maxM, maxO;
+    double baseline = 0;  // > 0: a stereo batch, with the `our` plane
 };
 
 // The device block of a batch of that size, carved: everything the LM's stages
@@ -100,7 +110,9 @@ int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bo
                        2 * P * s.nblk + 2 * P + nC + 3 * P + (want_S ? P * ld * ld + P * ld : 0) +
                        (want_dp ? 3 * nM : 0);
     const size_t ints = 2 * P + 3 * nO + P * (a.maxM + 1) + P * (a.maxC + 1) + nC + nM + 4 * P + (want_ids ? nM : 0);
-    const size_t bytes = sizeof(double) * dbl + sizeof(int) * ints + sizeof(float) * 2 * nO + nC + 64 * 256;
+    const bool stereo = a.baseline > 0;
+    const size_t bytes =
+        sizeof(double) * dbl + sizeof(int) * ints + sizeof(float) * (stereo ? 3 : 2) * nO + nC + 64 * 256;
     char* d = (char*)scratch(ctx, 11, bytes);
     if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     auto carve = [&](size_t n) {
@@ -155,6 +167,9 @@ int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bo
     s.pt_id = want_ids ? di(nM) : nullptr;
     s.oxy = (float*)carve(sizeof(float) * 2 * nO);
     s.fixed = (uint8_t*)carve(nC);
+    s.our = stereo ? (float*)carve(sizeof(float) * nO) : nullptr;
+    b.our = s.our;
+    b.baseline = a.baseline;
     b.n_cams = s.n_cams;
     b.n_points = s.n_points;
     b.ocam = s.ocam;
@@ -179,7 +194,7 @@ int stage(svo_ctx* ctx, const Args& a, bool want_S, bool want_dp, Staged& s) {
     const size_t P = (size_t)a.P, nC = P * a.maxC, nM = P * a.maxM, nO = P * a.maxO;
     std::vector<int> h_nc(P), h_nm(P), ocam(nO, 0), pt_off(P * (a.maxM + 1), 0), cam_off(P * (a.maxC + 1), 0),
         cam_idx(nO, 0), cam_pt(nO, 0), order((size_t)a.maxO);
-    std::vector<float> oxy(2 * nO, 0.f);
+    std::vector<float> oxy(2 * nO, 0.f), our(a.obs_ur ? nO : 0, 0.f);
     for (size_t p = 0; p < P; p++) {
         const int C = a.n_cams ? a.n_cams[p] : a.maxC, M = a.n_points ? a.n_points[p] : a.maxM;
         const int O = a.n_obs ? a.n_obs[p] : a.maxO;
@@ -197,10 +212,12 @@ int stage(svo_ctx* ctx, const Args& a, bool want_S, bool want_dp, Staged& s) {
             ocam[g] = cam[order[k]];
             oxy[2 * g] = a.obs_xy[2 * src];
             oxy[2 * g + 1] = a.obs_xy[2 * src + 1];
+            if (a.obs_ur) our[g] = a.obs_ur[src];
         }
         for (int k = 0; k < O; k++) cam_pt[p * a.maxO + k] = pt[order[cam_idx[p * a.maxO + k]]];
     }
-    int rc = alloc_staged(ctx, Sizes{a.P, a.maxC, a.maxM, a.maxO}, a.K, a.delta, want_S, want_dp, false, s);
+    int rc = alloc_staged(ctx, Sizes{a.P, a.maxC, a.maxM, a.maxO, a.obs_ur ? a.baseline : 0.0}, a.K, a.delta, want_S,
+                          want_dp, false, s);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     auto up = [&](void* dst, const void* src, size_t n) {
@@ -217,6 +234,7 @@ int stage(svo_ctx* ctx, const Args& a, bool want_S, bool want_dp, Staged& s) {
     SVO_HIP(ctx, up(s.pt_off, pt_off.data(), sizeof(int) * pt_off.size()));
     SVO_HIP(ctx, up(s.cam_off, cam_off.data(), sizeof(int) * cam_off.size()));
     SVO_HIP(ctx, up(s.oxy, oxy.data(), sizeof(float) * 2 * nO));
+    if (s.our) SVO_HIP(ctx, up(s.our, our.data(), sizeof(float) * nO));
     // the staging vectors go out of scope on return: the copies must have left them
     SVO_HIP(ctx, hipStreamSynchronize(st));
     return SVO_OK;
@@ -252,6 +270,7 @@ std::vector<uint8_t> non_finite(const Args& a) {
         for (int q = 0; q < 12 * C && ok; q++) ok = std::isfinite(a.poses[12 * p * a.maxC + q]);
         for (int q = 0; q < 3 * M && ok; q++) ok = std::isfinite(a.points[3 * p * a.maxM + q]);
         for (int q = 0; q < 2 * O && ok; q++) ok = std::isfinite(a.obs_xy[2 * p * a.maxO + q]);
+        for (int q = 0; q < O && ok && a.obs_ur; q++) ok = std::isfinite(a.obs_ur[p * a.maxO + q]);
         bad[p] = !ok;
     }
     return bad;
@@ -375,9 +394,10 @@ const char* check_lists(int P, int W, int cap, const int* counts, const int* ids
 }
 
 // ... and uploaded as they are (scratch slot 9)
-int upload_lists(svo_ctx* ctx, int P, int W, int cap, const int* counts, const int* ids, const float* xy, BaLists& l) {
+int upload_lists(svo_ctx* ctx, int P, int W, int cap, const int* counts, const int* ids, const float* xy, BaLists& l,
+                 const float* ur = nullptr) {
     const size_t nL = (size_t)P * W, nO = nL * cap;
-    char* in = (char*)scratch(ctx, 9, sizeof(int) * (nL + nO) + sizeof(float) * 2 * nO + 1024);
+    char* in = (char*)scratch(ctx, 9, sizeof(int) * (nL + nO) + sizeof(float) * (ur ? 3 : 2) * nO + 1024);
     if (!in) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     int* d_counts = (int*)in;
     int* d_ids = (int*)(in + ((sizeof(int) * nL + 255) & ~(size_t)255));
@@ -387,6 +407,11 @@ int upload_lists(svo_ctx* ctx, int P, int W, int cap, const int* counts, const i
     SVO_HIP(ctx, hipMemcpyAsync(d_ids, ids, sizeof(int) * nO, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * nO, hipMemcpyHostToDevice, st));
     l = BaLists{P, W, cap, nullptr, d_counts, d_ids, d_xy};
+    if (ur) {
+        float* d_ur = (float*)((char*)d_xy + ((sizeof(float) * 2 * nO + 255) & ~(size_t)255));
+        SVO_HIP(ctx, hipMemcpyAsync(d_ur, ur, sizeof(float) * nO, hipMemcpyHostToDevice, st));
+        l.ur = d_ur;
+    }
     return SVO_OK;
 }
 
@@ -395,11 +420,13 @@ int zero_observations(svo_ctx* ctx, const Staged& s) {
     const size_t nO = (size_t)s.b.P * s.b.maxO;
     for (int* a : {s.ocam, s.cam_idx, s.cam_pt}) SVO_HIP(ctx, hipMemsetAsync(a, 0, sizeof(int) * nO, ctx->stream));
     SVO_HIP(ctx, hipMemsetAsync(s.oxy, 0, sizeof(float) * 2 * nO, ctx->stream));
+    if (s.our) SVO_HIP(ctx, hipMemsetAsync(s.our, 0, sizeof(float) * nO, ctx->stream));
     return SVO_OK;
 }
 
 BaStageOut stage_out(const Staged& s, const double* map, int map_cap) {
     BaStageOut o;
+    o.our = s.our;
     o.maxM = s.b.maxM;
     o.maxO = s.b.maxO;
     o.ocam = s.ocam;
@@ -445,7 +472,9 @@ int svo::ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[
         maxO = std::max(maxO, h_no[p]);
     }
     Staged s;
-    if ((rc = alloc_staged(ctx, Sizes{l.P, l.W, maxM, maxO}, K, huber_delta, false, false, true, s))) return rc;
+    const double baseline = l.ur ? w.baseline : 0.0;
+    if ((rc = alloc_staged(ctx, Sizes{l.P, l.W, maxM, maxO, baseline}, K, huber_delta, false, false, true, s)))
+        return rc;
     if ((rc = zero_observations(ctx, s))) return rc;
     SVO_HIP(ctx, hipMemcpyAsync(s.n_cams, w.n_cams, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
     SVO_HIP(ctx, launch_ba_stage_fill(l, wk, stage_out(s, w.map, w.map_cap), st));
@@ -473,23 +502,27 @@ int svo::ba_adjust_device(svo_ctx* ctx, const BaDeviceWindow& w, const double K[
 
 extern "C" {
 
-int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
-                       const float* xy, int* ocam, float* oxy, int* pt_off, int* cam_off, int* cam_idx, int* cam_pt,
-                       int* pt_id, int* n_points, int* n_obs) {
-    if (!ctx) return SVO_ERR_ARG;
+// svo_ba_stage_lists, and with ur (not null) svo_ba_stage_lists_stereo
+static int stage_lists_entry(svo_ctx* ctx, const char* who, int n_problems, int n_cams, int cap, const int* counts,
+                             const int* ids, const float* xy, const float* ur, int* ocam, float* oxy, float* our,
+                             int* pt_off, int* cam_off, int* cam_idx, int* cam_pt, int* pt_id, int* n_points,
+                             int* n_obs) {
     if (const char* why = check_lists(n_problems, n_cams, cap, counts, ids, xy))
-        return set_error(ctx, SVO_ERR_ARG, "svo_ba_stage_lists: %s", why);
+        return set_error(ctx, SVO_ERR_ARG, "%s: %s", who, why);
     if (n_problems == 0) return SVO_OK;
     const size_t P = (size_t)n_problems, WC = (size_t)n_cams * cap, nO = P * WC;
     // the outputs are a block of the BA's own layout with max_points = max_obs = n_cams * cap
     hipStream_t st = ctx->stream;
     BaLists l;
     BaStageWork wk;
-    int rc = upload_lists(ctx, n_problems, n_cams, cap, counts, ids, xy, l);
+    int rc = upload_lists(ctx, n_problems, n_cams, cap, counts, ids, xy, l, ur);
     if (rc || (rc = stage_work(ctx, l, wk))) return rc;
     const double K[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     Staged s;
-    if ((rc = alloc_staged(ctx, Sizes{n_problems, n_cams, (int)WC, (int)WC}, K, 0.0, false, false, true, s))) return rc;
+    // (the baseline only asks for the `our` plane: no BA kernel runs here)
+    if ((rc = alloc_staged(ctx, Sizes{n_problems, n_cams, (int)WC, (int)WC, ur ? 1.0 : 0.0}, K, 0.0, false, false, true,
+                           s)))
+        return rc;
     if ((rc = zero_observations(ctx, s))) return rc;
     SVO_HIP(ctx, hipMemsetAsync(s.pt_id, 0, sizeof(int) * nO, st));
     SVO_HIP(ctx, launch_ba_stage_place(l, wk, st));
@@ -500,6 +533,7 @@ int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const 
     };
     SVO_HIP(ctx, down(ocam, s.ocam, sizeof(int) * nO));
     SVO_HIP(ctx, down(oxy, s.oxy, sizeof(float) * 2 * nO));
+    if (s.our) SVO_HIP(ctx, down(our, s.our, sizeof(float) * nO));
     SVO_HIP(ctx, down(pt_off, s.pt_off, sizeof(int) * P * (WC + 1)));
     SVO_HIP(ctx, down(cam_off, s.cam_off, sizeof(int) * P * (n_cams + 1)));
     SVO_HIP(ctx, down(cam_idx, s.cam_idx, sizeof(int) * nO));
@@ -508,6 +542,23 @@ int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const 
     SVO_HIP(ctx, down(n_points, s.n_points, sizeof(int) * P));
     SVO_HIP(ctx, down(n_obs, wk.n_obs, sizeof(int) * P));
     return SVO_OK;
+}
+
+int svo_ba_stage_lists(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                       const float* xy, int* ocam, float* oxy, int* pt_off, int* cam_off, int* cam_idx, int* cam_pt,
+                       int* pt_id, int* n_points, int* n_obs) {
+    if (!ctx) return SVO_ERR_ARG;
+    return stage_lists_entry(ctx, "svo_ba_stage_lists", n_problems, n_cams, cap, counts, ids, xy, nullptr, ocam, oxy,
+                             nullptr, pt_off, cam_off, cam_idx, cam_pt, pt_id, n_points, n_obs);
+}
+
+int svo_ba_stage_lists_stereo(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
+                              const float* xy, const float* ur, int* ocam, float* oxy, float* our, int* pt_off,
+                              int* cam_off, int* cam_idx, int* cam_pt, int* pt_id, int* n_points, int* n_obs) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (n_problems > 0 && !ur) return set_error(ctx, SVO_ERR_ARG, "svo_ba_stage_lists_stereo: ur is null");
+    return stage_lists_entry(ctx, "svo_ba_stage_lists_stereo", n_problems, n_cams, cap, counts, ids, xy, ur, ocam, oxy,
+                             our, pt_off, cam_off, cam_idx, cam_pt, pt_id, n_points, n_obs);
 }
 
 int svo_ba_time_staging(svo_ctx* ctx, int n_problems, int n_cams, int cap, const int* counts, const int* ids,
@@ -610,17 +661,14 @@ int svo_ba_sort_observations(const int* obs_cam, const int* obs_point, int n_obs
     return SVO_OK;
 }
 
-int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
-                     const int* n_points, const int* n_obs, const double* poses, const uint8_t* fixed,
-                     const double* points, const int* obs_cam, const int* obs_point, const float* obs_xy,
-                     const double K[9], double huber_delta, double lambda, double* U, double* gc, double* V,
-                     double* gp, double* cost, double* S, double* b, double* dc, double* dp, int* n_free,
-                     int* status) {
-    if (!ctx) return SVO_ERR_ARG;
-    const Args a{n_problems, max_cams, max_points, max_obs, n_cams, n_points, n_obs, poses,
-                 fixed,      points,   obs_cam,    obs_point, obs_xy, K,       huber_delta};
-    if (const char* why = check(a)) return set_error(ctx, SVO_ERR_ARG, "svo_ba_linearize: %s", why);
-    if (!(lambda >= 0) || !std::isfinite(lambda)) return set_error(ctx, SVO_ERR_ARG, "svo_ba_linearize: lambda");
+// svo_ba_linearize and svo_ba_linearize_stereo (a.obs_ur set, checked by the caller)
+static int linearize_entry(svo_ctx* ctx, const char* who, const Args& a, double lambda, double* U, double* gc,
+                           double* V, double* gp, double* cost, double* S, double* b, double* dc, double* dp,
+                           int* n_free, int* status) {
+    const int n_problems = a.P, max_cams = a.maxC, max_points = a.maxM;
+    const int *n_cams = a.n_cams, *n_points = a.n_points;
+    if (const char* why = check(a)) return set_error(ctx, SVO_ERR_ARG, "%s: %s", who, why);
+    if (!(lambda >= 0) || !std::isfinite(lambda)) return set_error(ctx, SVO_ERR_ARG, "%s: lambda", who);
     if (n_problems == 0) return SVO_OK;
     Staged s;
     int rc = stage(ctx, a, S || b, dp != nullptr, s);
@@ -678,15 +726,40 @@ int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points,
     return SVO_OK;
 }
 
-int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
-                      const int* n_points, const int* n_obs, double* poses, const uint8_t* fixed, double* points,
-                      const int* obs_cam, const int* obs_point, const float* obs_xy, const double K[9],
-                      double huber_delta, int max_iterations, double* costs, int* iterations) {
+int svo_ba_linearize(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
+                     const int* n_points, const int* n_obs, const double* poses, const uint8_t* fixed,
+                     const double* points, const int* obs_cam, const int* obs_point, const float* obs_xy,
+                     const double K[9], double huber_delta, double lambda, double* U, double* gc, double* V,
+                     double* gp, double* cost, double* S, double* b, double* dc, double* dp, int* n_free,
+                     int* status) {
     if (!ctx) return SVO_ERR_ARG;
     const Args a{n_problems, max_cams, max_points, max_obs, n_cams, n_points, n_obs, poses,
                  fixed,      points,   obs_cam,    obs_point, obs_xy, K,       huber_delta};
-    if (const char* why = check(a)) return set_error(ctx, SVO_ERR_ARG, "svo_bundle_adjust: %s", why);
-    if (max_iterations < 0) return set_error(ctx, SVO_ERR_ARG, "svo_bundle_adjust: max_iterations < 0");
+    return linearize_entry(ctx, "svo_ba_linearize", a, lambda, U, gc, V, gp, cost, S, b, dc, dp, n_free, status);
+}
+
+int svo_ba_linearize_stereo(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs,
+                            const int* n_cams, const int* n_points, const int* n_obs, const double* poses,
+                            const uint8_t* fixed, const double* points, const int* obs_cam, const int* obs_point,
+                            const float* obs_xy, const float* obs_ur, double baseline, const double K[9],
+                            double huber_delta, double lambda, double* U, double* gc, double* V, double* gp,
+                            double* cost, double* S, double* b, double* dc, double* dp, int* n_free, int* status) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (const char* why = check_stereo(obs_ur, baseline))
+        return set_error(ctx, SVO_ERR_ARG, "svo_ba_linearize_stereo: %s", why);
+    const Args a{n_problems, max_cams, max_points, max_obs, n_cams,      n_points, n_obs,  poses,   fixed,
+                 points,     obs_cam,  obs_point,  obs_xy,  K,           huber_delta,      obs_ur,  baseline};
+    return linearize_entry(ctx, "svo_ba_linearize_stereo", a, lambda, U, gc, V, gp, cost, S, b, dc, dp, n_free,
+                           status);
+}
+
+// svo_bundle_adjust and svo_bundle_adjust_stereo (a.obs_ur set, checked by the caller)
+static int adjust_entry(svo_ctx* ctx, const char* who, const Args& a, double* poses, double* points,
+                        int max_iterations, double* costs, int* iterations) {
+    const int n_problems = a.P, max_cams = a.maxC, max_points = a.maxM;
+    const int *n_cams = a.n_cams, *n_points = a.n_points;
+    if (const char* why = check(a)) return set_error(ctx, SVO_ERR_ARG, "%s: %s", who, why);
+    if (max_iterations < 0) return set_error(ctx, SVO_ERR_ARG, "%s: max_iterations < 0", who);
     if (n_problems == 0) return SVO_OK;
     Staged s;
     int rc = stage(ctx, a, false, false, s);
@@ -711,6 +784,29 @@ int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points
         if (iterations) iterations[p] = its[p];
     }
     return SVO_OK;
+}
+
+int svo_bundle_adjust(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,
+                      const int* n_points, const int* n_obs, double* poses, const uint8_t* fixed, double* points,
+                      const int* obs_cam, const int* obs_point, const float* obs_xy, const double K[9],
+                      double huber_delta, int max_iterations, double* costs, int* iterations) {
+    if (!ctx) return SVO_ERR_ARG;
+    const Args a{n_problems, max_cams, max_points, max_obs, n_cams, n_points, n_obs, poses,
+                 fixed,      points,   obs_cam,    obs_point, obs_xy, K,       huber_delta};
+    return adjust_entry(ctx, "svo_bundle_adjust", a, poses, points, max_iterations, costs, iterations);
+}
+
+int svo_bundle_adjust_stereo(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs,
+                             const int* n_cams, const int* n_points, const int* n_obs, double* poses,
+                             const uint8_t* fixed, double* points, const int* obs_cam, const int* obs_point,
+                             const float* obs_xy, const float* obs_ur, double baseline, const double K[9],
+                             double huber_delta, int max_iterations, double* costs, int* iterations) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (const char* why = check_stereo(obs_ur, baseline))
+        return set_error(ctx, SVO_ERR_ARG, "svo_bundle_adjust_stereo: %s", why);
+    const Args a{n_problems, max_cams, max_points, max_obs, n_cams,      n_points, n_obs,  poses,   fixed,
+                 points,     obs_cam,  obs_point,  obs_xy,  K,           huber_delta,      obs_ur,  baseline};
+    return adjust_entry(ctx, "svo_bundle_adjust_stereo", a, poses, points, max_iterations, costs, iterations);
 }
 
 int svo_ba_time_iteration(svo_ctx* ctx, int n_problems, int max_cams, int max_points, int max_obs, const int* n_cams,

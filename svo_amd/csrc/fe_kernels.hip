@@ -439,6 +439,7 @@ __device__ __forceinline__ void append_body(const AppendBatch& A, int s, int n0,
             A.xy[2 * f] = xl;
             A.xy[2 * f + 1] = yl;
             A.mid[f] = m0 + d;
+            if (A.ur) A.ur[f] = A.st_next[2 * (o + j)];
             // left camera frame (double of the float point, as Eigen::Vector3d{p_w.x,
             // p_w.y, p_w.z}); the pose is applied once known (PendingMap)
             double* X = A.map + 3 * ((size_t)s * A.map_cap + m0 + d);
@@ -526,7 +527,9 @@ __global__ __launch_bounds__(kFeBlock) void stereo_prep_kernel(StereoPrepBatch B
 // stamped with the map epoch its ids belong to.
 __global__ __launch_bounds__(kFeBlock) void window_record_kernel(WindowRing R, int slot, const int* __restrict__ n_in,
                                                                  const float* __restrict__ xy_in,
-                                                                 const int* __restrict__ mid_in) {
+                                                                 const int* __restrict__ mid_in,
+                                                                 const float* __restrict__ ur_in,
+                                                                 const int* __restrict__ added) {
     const int s = blockIdx.x;
     const int n = min(max(n_in[s], 0), R.cap);
     const size_t src = (size_t)s * R.cap, dst = ((size_t)s * R.window + slot) * R.cap;
@@ -535,6 +538,10 @@ __global__ __launch_bounds__(kFeBlock) void window_record_kernel(WindowRing R, i
     for (int i = threadIdx.x; i < n; i += kFeBlock) {
         b[i] = a[i];
         R.mid[dst + i] = mid_in[src + i];
+    }
+    if (R.ur) {  // the frame's own features are the last added[s] of its list
+        const int n0 = max(n_in[s] - max(added[s], 0), 0);
+        for (int i = threadIdx.x; i < n; i += kFeBlock) R.ur[dst + i] = i < n0 ? -1.f : ur_in[src + i];
     }
     if (threadIdx.x == 0) {
         R.n[s * R.window + slot] = n;
@@ -567,10 +574,10 @@ __global__ __launch_bounds__(64) void window_select_kernel(WindowRing R, WindowO
 
 }  // namespace
 
-hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid, int nseq,
-                                hipStream_t st) {
-    if (slot < 0 || slot >= r.window) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(window_record_kernel, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid);
+hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid,
+                                const float* ur, const int* added, int nseq, hipStream_t st) {
+    if (slot < 0 || slot >= r.window || (r.ur && (!ur || !added))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_record_kernel, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid, ur, added);
     return hipGetLastError();
 }
 

@@ -119,6 +119,10 @@ struct AppendBatch {
     int* h_n;     // nullable, host-coherent
     int* h_added; // nullable, host-coherent
     const float4* st_X;  // stereo_tri_kernel's filter + DLT of st_xy[0, n) (x, y, z, keep)
+    // the stereo window only (both null otherwise): the appended features' right
+    // columns, st_next's x of their matches, into ur [s][cap] at the features' places
+    const float* st_next;
+    float* ur;
 };
 hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st);
 
@@ -178,10 +182,14 @@ struct WindowRing {
     float* xy;       // [s][window][cap][2]
     int* mid;        // [s][window][cap], strictly increasing per slot
     int* map_epoch;  // [s]
+    float* ur;       // [s][window][cap], the stereo window only (null otherwise): the right
+                     // column of the match that created the feature in this frame, -1 if tracked
 };
-// xyA / midA / nA as the step leaves them into `slot` of every sequence
-hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid, int nseq,
-                                hipStream_t st);
+// xyA / midA / nA as the step leaves them into `slot` of every sequence; with a
+// stereo ring also ur [s][cap] (AppendBatch::ur) for the last added[s] features of
+// each list, the frame's new ones, and -1 for the tracked ones in front of them
+hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid,
+                                const float* ur, const int* added, int nseq, hipStream_t st);
 // The recorded slots, oldest first (the same for every sequence: the ring turns
 // in lockstep); per sequence those of the current epoch are valid:
 // sel_slot / sel_cnt [s][window] (the valid slots first, zero counts behind), n_cams [s].

@@ -2,6 +2,7 @@
 // observation window and its bundle adjustment, level readbacks, the timing
 // probes and the phase-timing ring.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "ba.hpp"
@@ -149,7 +150,13 @@ int svo_frontend_map_points(svo_frontend* fe, int seq, double* xyz, int cap, int
     return SVO_OK;
 }
 
-int svo_frontend_window_enable(svo_frontend* fe, int window) {
+// the rig's baseline from the rectified projection matrices: P_right = K [I | (-b, 0, 0)]
+static double fe_baseline(const svo_frontend* fe) {
+    return -(double)fe->cfg.P_right[3] / (double)fe->cfg.P_right[0];
+}
+
+// svo_frontend_window_enable, and with the right columns svo_frontend_window_enable_stereo
+static int fe_window_enable(svo_frontend* fe, int window, bool stereo) {
     if (!fe) return SVO_ERR_ARG;
     svo_ctx* ctx = fe->ctx;
     FeWindow& w = fe->win;
@@ -157,6 +164,8 @@ int svo_frontend_window_enable(svo_frontend* fe, int window) {
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable: window outside 1 .. SVO_BA_MAX_CAMS");
     if (fe->ahead.stepped >= 0 || w.slots)
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable: once, before svo_frontend_init");
+    if (stereo && !(std::isfinite(fe_baseline(fe)) && fe_baseline(fe) > 0))
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable_stereo: P_right gives no baseline > 0");
     const size_t S = fe->S, Wn = window, CAP = fe->CAP;
     size_t bytes = 0;
     char* const base0 = nullptr;
@@ -164,6 +173,7 @@ int svo_frontend_window_enable(svo_frontend* fe, int window) {
         if (pass == 1 && hipMalloc(&w.mem, bytes) != hipSuccess) {
             w.mem = nullptr;
             w.ring = WindowRing{};  // (the sizing pass left offsets in it)
+            w.ur_feat = nullptr;
             return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: hipMalloc(%zu)", bytes);
         }
         char* p = pass == 0 ? base0 : (char*)w.mem;
@@ -177,6 +187,8 @@ int svo_frontend_window_enable(svo_frontend* fe, int window) {
         w.sel_slot = carve<int>(p, S * Wn);
         w.sel_cnt = carve<int>(p, S * Wn);
         w.sel_nc = carve<int>(p, S);
+        w.ring.ur = stereo ? carve<float>(p, S * Wn * CAP) : nullptr;
+        w.ur_feat = stereo ? carve<float>(p, S * CAP) : nullptr;
         bytes = (size_t)(p - (pass == 0 ? base0 : (char*)w.mem)) + 256;
     }
     if (hipHostMalloc((void**)&w.h_pose, sizeof(double) * 12 * S * Wn, hipHostMallocCoherent | hipHostMallocMapped) !=
@@ -185,6 +197,7 @@ int svo_frontend_window_enable(svo_frontend* fe, int window) {
         w.mem = nullptr;
         w.h_pose = nullptr;
         w.ring = WindowRing{};
+        w.ur_feat = nullptr;
         return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: host-coherent poses");
     }
     std::memset(w.h_pose, 0, sizeof(double) * 12 * S * Wn);
@@ -195,6 +208,10 @@ int svo_frontend_window_enable(svo_frontend* fe, int window) {
     w.slots = window;
     return SVO_OK;
 }
+
+int svo_frontend_window_enable(svo_frontend* fe, int window) { return fe_window_enable(fe, window, false); }
+
+int svo_frontend_window_enable_stereo(svo_frontend* fe, int window) { return fe_window_enable(fe, window, true); }
 
 int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* frame_t, double* poses, int* counts,
                         int* ids, float* xy) {
@@ -234,12 +251,45 @@ int svo_frontend_window(svo_frontend* fe, int seq, int cap, int* n_frames, int* 
     return SVO_OK;
 }
 
-int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations, double* costs,
-                               int* iterations, int* sizes) {
+int svo_frontend_window_right(svo_frontend* fe, int seq, int cap, float* ur) {
+    if (!fe || seq < 0 || seq >= fe->S || cap < 0) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    const FeWindow& w = fe->win;
+    if (!w.ring.ur) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_right: no stereo window enabled");
+    int rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    const size_t Wn = w.slots, CAP = fe->CAP;
+    std::vector<int> n(Wn), ep(Wn);
+    int cur = 0;
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(n.data(), w.ring.n + seq * Wn, sizeof(int) * Wn, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(ep.data(), w.ring.epoch + seq * Wn, sizeof(int) * Wn, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(&cur, w.ring.map_epoch + seq, sizeof(int), hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    const WindowOrder o = fe_window_order(fe);
+    int v = 0;
+    for (int i = 0; i < o.n; i++) {  // svo_frontend_window's walk
+        const int sl = o.slot[i];
+        if (ep[sl] != cur) continue;
+        const int k = std::min(n[sl], cap);
+        if (ur && k > 0)
+            SVO_HIP(ctx, hipMemcpyAsync(ur + (size_t)v * cap, w.ring.ur + (seq * Wn + sl) * CAP, sizeof(float) * k,
+                                        hipMemcpyDeviceToHost, st));
+        v++;
+    }
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+// svo_frontend_bundle_adjust, and with the ring's right columns svo_frontend_bundle_adjust_stereo
+static int fe_bundle_adjust(svo_frontend* fe, bool stereo, int n_fixed, double huber_delta, int max_iterations,
+                            double* costs, int* iterations, int* sizes) {
     if (!fe) return SVO_ERR_ARG;
     svo_ctx* ctx = fe->ctx;
     const FeWindow& w = fe->win;
     if (!w.slots) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_bundle_adjust: no window enabled");
+    if (stereo && !w.ring.ur)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_bundle_adjust_stereo: no stereo window enabled");
     if (n_fixed < 0 || max_iterations < 0)
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_bundle_adjust: n_fixed / max_iterations < 0");
     // the newest frame's pose lands and its keyframe's points reach the world frame
@@ -253,7 +303,21 @@ int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta
     bw.map = fe->map;
     bw.map_cap = fe->MAPCAP;
     bw.n_fixed = n_fixed;
+    if (stereo) {
+        bw.lists.ur = w.ring.ur;
+        bw.baseline = fe_baseline(fe);
+    }
     return ba_adjust_device(ctx, bw, fe->cfg.K, huber_delta, max_iterations, costs, iterations, sizes);
+}
+
+int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations, double* costs,
+                               int* iterations, int* sizes) {
+    return fe_bundle_adjust(fe, false, n_fixed, huber_delta, max_iterations, costs, iterations, sizes);
+}
+
+int svo_frontend_bundle_adjust_stereo(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations,
+                                      double* costs, int* iterations, int* sizes) {
+    return fe_bundle_adjust(fe, true, n_fixed, huber_delta, max_iterations, costs, iterations, sizes);
 }
 
 int svo_frontend_scharr_level(svo_frontend* fe, int seq, int t, int level, int16_t* ix, int16_t* iy, int stride) {

@@ -193,6 +193,8 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
     ab.h_n = fe->h_nA;
     ab.h_added = fe->h_added;
     ab.st_X = fe->st_X;
+    ab.st_next = fe->st_next;
+    ab.ur = fe->win.ur_feat;  // (null without a stereo window)
     if (spec) {
         ph_begin(fe, PH_TAIL, st, &slot);
         SVO_HIP(ctx, launch_keyframe_fused(tb, ab, fe->S, st));
@@ -291,7 +293,7 @@ int fe_window_record(svo_frontend* fe, int t, hipStream_t st) {
     FeWindow& w = fe->win;
     if (!w.slots) return SVO_OK;
     const int slot = w.count % w.slots;
-    SVO_HIP(fe->ctx, launch_window_record(w.ring, slot, fe->nA, fe->xyA, fe->midA, fe->S, st));
+    SVO_HIP(fe->ctx, launch_window_record(w.ring, slot, fe->nA, fe->xyA, fe->midA, w.ur_feat, fe->added, fe->S, st));
     w.frame[slot] = t;
     w.count++;
     for (int s = 0; s < fe->S; s++) {

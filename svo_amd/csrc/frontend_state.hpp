@@ -117,6 +117,9 @@ struct FeWindow {
     WindowRing ring{};
     int *sel_slot = nullptr, *sel_cnt = nullptr, *sel_nc = nullptr;  // launch_window_select's outputs
     double* h_pose = nullptr;  // host-coherent [s][slots][12]: the slots' poses, world -> camera
+    // svo_frontend_window_enable_stereo only: the current list's right columns
+    // [s][cap] (the append writes its new features'), recorded into ring.ur
+    float* ur_feat = nullptr;
 };
 
 }  // namespace svo
