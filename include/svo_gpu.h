@@ -23,6 +23,10 @@
  *     fit on the inliers, R:src/tracking.cpp:191-196)
  *   cv::triangulatePoints + convertPointsFromHomogeneous          svo_triangulate_points
  *     R:src/tracking.cpp:125-131
+ *   (not in the reference, which is fed rectified pairs:)
+ *   cv::initUndistortRectifyMap(..., CV_16SC2, ...)              svo_init_undistort_rectify_map
+ *   cv::remap(..., INTER_LINEAR, BORDER_CONSTANT, 0)             svo_remap / svo_image_upload_raw /
+ *                                                                svo_frontend_set_rectification
  *
  * Conventions (no exceptions cross this ABI; no torch types):
  *   - Host memory is caller-owned. Device memory is owned by the context.
@@ -93,6 +97,46 @@ int svo_image_upload(svo_ctx* ctx, svo_image* img, const uint8_t* gray, int stri
  * 0 (OpenCV's fixed-point weights, bit-exact), then the pyramid build. Returns
  * once the copy is queued: `bgr` may be reused immediately. */
 int svo_image_upload_bgr(svo_ctx* ctx, svo_image* img, const uint8_t* bgr, int stride);
+/* Rectification of raw camera frames on the device. The reference never
+ * rectifies (KITTI odometry ships rectified pairs); a rig of real lenses needs
+ * cv::initUndistortRectifyMap + cv::remap on both eyes of every frame first.
+ *
+ * svo_rect_maps: one camera's map pair, device-resident -- exactly the two arrays
+ * cv::initUndistortRectifyMap(..., CV_16SC2, map1, map2) or cv::convertMaps
+ * produce (any camera model: fisheye or thin-prism users hand in OpenCV's own
+ * maps): map1 int16 [h][w][2] = (sx, sy), map2 uint16 [h][w] < 1024 holding the
+ * fractions a = map2 & 31 (x) and b = map2 >> 5 (y) in 1/32 pixel. raw_w x raw_h:
+ * the camera's frame, w x h: the rectified image. SVO_ERR_ARG (nothing written):
+ * null arguments, raw_w or raw_h < 2, w or h < 1, a map2 value >= 1024. */
+typedef struct svo_rect_maps svo_rect_maps;
+int svo_rect_maps_create(svo_ctx* ctx, int raw_w, int raw_h, int w, int h, const int16_t* map1,
+                         const uint16_t* map2, svo_rect_maps** out);
+void svo_rect_maps_destroy(svo_ctx* ctx, svo_rect_maps* maps);
+/* cv::initUndistortRectifyMap(K, dist, R, newK, Size(w, h), CV_16SC2, map1, map2)
+ * for the rational model dist = (k1, k2, p1, p2, k3, k4, k5, k6), on the host (no
+ * context; once per rig): f64 in the order of OpenCV's scalar loop (iR = (newK
+ * R)^-1 by cofactors, running sums along a row), coordinates rounded half to
+ * even at 1/32 pixel. One deviation: the int16 cast of map1 saturates where
+ * OpenCV's truncates, so a coordinate far outside stays outside. SVO_ERR_ARG
+ * (nothing written): null arguments, w or h < 1, det(newK R) zero or not finite. */
+int svo_init_undistort_rectify_map(const double K[9], const double dist[8], const double R[9], const double newK[9],
+                                   int w, int h, int16_t* map1, uint16_t* map2);
+/* cv::remap(src, dst, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) of an 8U
+ * raw_w x raw_h host image into a w x h host image (rows stride / dst_stride bytes
+ * apart), through the kernel the entry points below use: with tap(i, j) = src[sy +
+ * i][sx + j] inside the image and 0 outside,
+ *   dst = ((32-a)(32-b) tap(0,0) + a(32-b) tap(0,1) + (32-a)b tap(1,0) + ab tap(1,1) + 512) >> 10,
+ * OpenCV's fixed-point arithmetic restated without its weight table (DESIGN.md
+ * section 3b). bgr != 0: src is 8UC3 and every tap its grey value first, i.e.
+ * cv::cvtColor(BGR2GRAY) then cv::remap. Synchronous. */
+int svo_remap(svo_ctx* ctx, const uint8_t* src, int stride, int bgr, const svo_rect_maps* maps, uint8_t* dst,
+              int dst_stride);
+/* svo_image_upload / svo_image_upload_bgr from a raw frame: H2D of the raw_w x
+ * raw_h frame, svo_remap's rule written straight into level 0, then the pyramid
+ * build. Returns once the frame has left `raw` (kernel and pyramid still queued).
+ * SVO_ERR_ARG: the image is not the maps' w x h, stride below a raw row. */
+int svo_image_upload_raw(svo_ctx* ctx, svo_image* img, const uint8_t* raw, int stride, int bgr,
+                         const svo_rect_maps* maps);
 /* Rebuild levels 1..max_levels from the device-resident level 0. */
 int svo_image_build_pyramid(svo_ctx* ctx, svo_image* img);
 int svo_image_level_size(const svo_image* img, int level, int* w, int* h);
@@ -494,6 +538,19 @@ int svo_frontend_set_frame(svo_frontend* fe, int seq, int t, const uint8_t* left
 /* Same from BGR 8UC3 frames (svo_image_upload_bgr's conversion). */
 int svo_frontend_set_frame_bgr(svo_frontend* fe, int seq, int t, const uint8_t* left_bgr,
                                const uint8_t* right_bgr, int stride);
+/* Raw frames: from this call on svo_frontend_set_frame, svo_frontend_set_frame_bgr
+ * and svo_frontend_queue_frames take the cameras' raw frames (the maps' raw_w x
+ * raw_h, which may differ from the config's size: stride checks and copies use it)
+ * and level 0 of every slot is cv::remap of them with that eye's maps (svo_remap's
+ * rule; BGR: grey taps), in place of cv::initUndistortRectifyMap + cv::remap on
+ * the host. The streamed path rectifies where it converted, on the upload stream
+ * with the same events; the resident path stages the raw pair first (raw frames
+ * are not kept). Nothing downstream of level 0 changes; a front end that never
+ * calls this launches exactly what it did. Once, before the first set_frame,
+ * queue_frames or init; the maps must outlive the front end. SVO_ERR_ARG: called
+ * later or twice, maps whose w x h is not the config's, eyes of different raw
+ * sizes, null arguments. */
+int svo_frontend_set_rectification(svo_frontend* fe, const svo_rect_maps* left, const svo_rect_maps* right);
 /* Streamed frames (R:include/async_image_loader.h:36-69: the loader hands each
  * stereo pair to Tracking as it arrives; here a whole step's worth at once):
  * queue frame t of every sequence -- left[s] / right[s] (grey, or BGR 8UC3 when
@@ -612,6 +669,14 @@ int svo_frontend_pyramid_level(svo_frontend* fe, int seq, int t, int right, int 
  * context stream: reps rebuilds (identical contents) after one warm-up, HIP
  * events around them; ms per chain. Synchronises the front end first. */
 int svo_frontend_time_pyramid(svo_frontend* fe, int t, int reps, double* ms_per_launch);
+/* The streamed path's level-0 write of the left eye (every sequence) timed alone the
+ * same way, from the staging block as the last svo_frontend_queue_frames left it
+ * (its stride, grey or BGR) into ring slot t % n_frames: rectify != 0 the
+ * rectifying kernel with the left maps, 0 the plain copy / conversion kernel
+ * (the staged frames must be at least the config's size). Synchronises the front
+ * end first; the slot's image is overwritten. SVO_ERR_ARG: nothing was queued,
+ * rectify without svo_frontend_set_rectification. */
+int svo_frontend_time_ingest(svo_frontend* fe, int t, int rectify, int reps, double* ms_per_launch);
 /* The front end's FAST detection of frame t (every sequence; FAST-9 + cornerScore +
  * NMS without the box mask, i.e. the pre-detection stage: extractFeatures' detector,
  * R:src/tracking.cpp:82) timed alone the same way; ms per launch (row-count reset +

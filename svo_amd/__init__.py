@@ -35,6 +35,7 @@ __all__ = [
     "SvoError", "lib", "Context", "Image", "FastFeatureDetector",
     "TERM_COUNT", "TERM_EPS", "LK_USE_INITIAL_FLOW", "LK_GET_MIN_EIGENVALS", "LK_OPENCV_ORDER",
     "lib_path", "Frontend", "FrontendConfig", "FrontendStats",
+    "RectMaps", "init_undistort_rectify_map", "remap",
 ]
 
 TERM_COUNT = 1
@@ -63,11 +64,12 @@ def lib_path() -> str:
 # holds its front end and its context; the weak sets below are cleared before
 # their __del__ run), so a context also keeps the native handles of its live
 # dependants (Context._deps) and destroys those first when it goes first.
-_LIVE = {"frontend": weakref.WeakSet(), "image": weakref.WeakSet(), "context": weakref.WeakSet()}
+_LIVE = {"frontend": weakref.WeakSet(), "image": weakref.WeakSet(), "maps": weakref.WeakSet(),
+         "context": weakref.WeakSet()}
 
 
 def _close_all():
-    for kind in ("frontend", "image", "context"):
+    for kind in ("frontend", "image", "maps", "context"):
         for obj in list(_LIVE[kind]):
             try:
                 obj.close()
@@ -102,6 +104,13 @@ _SIGS = [
     ("svo_image_upload", C.c_int, [_vp, _vp, _u8p, C.c_int]),
     ("svo_image_upload_bgr", C.c_int, [_vp, _vp, _u8p, C.c_int]),
     ("svo_image_build_pyramid", C.c_int, [_vp, _vp]),
+    ("svo_rect_maps_create", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16),
+                                       C.POINTER(C.c_uint16), C.POINTER(_vp)]),
+    ("svo_rect_maps_destroy", None, [_vp, _vp]),
+    ("svo_init_undistort_rectify_map", C.c_int, [_f64p, _f64p, _f64p, _f64p, C.c_int, C.c_int, C.POINTER(C.c_int16),
+                                                 C.POINTER(C.c_uint16)]),
+    ("svo_remap", C.c_int, [_vp, _u8p, C.c_int, C.c_int, _vp, _u8p, C.c_int]),
+    ("svo_image_upload_raw", C.c_int, [_vp, _vp, _u8p, C.c_int, C.c_int, _vp]),
     ("svo_image_level_size", C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     ("svo_image_download_level", C.c_int, [_vp, _vp, C.c_int, _u8p, C.c_int]),
     ("svo_image_scharr_level", C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int16), C.POINTER(C.c_int16), C.c_int]),
@@ -151,6 +160,8 @@ _SIGS = [
     ("svo_frontend_destroy", None, [_vp]),
     ("svo_frontend_set_frame", C.c_int, [_vp, C.c_int, C.c_int, _u8p, _u8p, C.c_int]),
     ("svo_frontend_set_frame_bgr", C.c_int, [_vp, C.c_int, C.c_int, _u8p, _u8p, C.c_int]),
+    ("svo_frontend_set_rectification", C.c_int, [_vp, _vp, _vp]),
+    ("svo_frontend_time_ingest", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_map_points", C.c_int, [_vp, C.c_int, _f64p, C.c_int, _i32p]),
     ("svo_frontend_window_enable", C.c_int, [_vp, C.c_int]),
     ("svo_frontend_window", C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _f64p, _i32p, _i32p, _f32p]),
@@ -318,6 +329,17 @@ class Image:
         assert bgr.shape == (self.h, self.w, 3)
         self.ctx._check(lib().svo_image_upload_bgr(self.ctx.handle, self.handle, _p(bgr, _u8p), 3 * self.w))
 
+    def upload_raw(self, raw: np.ndarray, maps: "RectMaps"):
+        """H2D of a raw camera frame ((raw_h, raw_w) grey or (raw_h, raw_w, 3) BGR),
+        rectified on the device into level 0 (cv::remap with `maps`), then the pyramid
+        (svo_image_upload_raw)."""
+        raw = _c(raw, np.uint8)
+        bgr = raw.ndim == 3
+        if raw.shape != (maps.raw_h, maps.raw_w) + ((3,) if bgr else ()):
+            raise SvoError(f"upload_raw: a raw frame of {maps.raw_h} x {maps.raw_w} expected, got {raw.shape}")
+        self.ctx._check(lib().svo_image_upload_raw(self.ctx.handle, self.handle, _p(raw, _u8p),
+                                                   raw.shape[1] * (3 if bgr else 1), int(bgr), maps.handle))
+
     def close(self):
         if self.handle:
             if self.ctx._deps.pop(self.handle.value, None):  # (else the context went first and took it along)
@@ -329,6 +351,75 @@ class Image:
             self.close()
         except Exception:
             pass
+
+
+_i16p = C.POINTER(C.c_int16)
+_u16p = C.POINTER(C.c_uint16)
+
+
+def init_undistort_rectify_map(K, dist, R, newK, w, h):
+    """cv::initUndistortRectifyMap(K, dist, R, newK, (w, h), CV_16SC2) -> (map1 (h, w, 2)
+    int16, map2 (h, w) uint16); dist: up to 8 coefficients (k1, k2, p1, p2, k3, k4,
+    k5, k6), zero-filled (svo_init_undistort_rectify_map: host code, no GPU context)."""
+    d = np.zeros(8)
+    dist = np.asarray(dist, np.float64).ravel()
+    if len(dist) > 8:
+        raise SvoError("init_undistort_rectify_map: at most 8 distortion coefficients")
+    d[:len(dist)] = dist
+    K, R, newK = (_c(m, np.float64).reshape(9) for m in (K, R, newK))
+    map1 = np.zeros((max(h, 0), max(w, 0), 2), np.int16)
+    map2 = np.zeros((max(h, 0), max(w, 0)), np.uint16)
+    rc = lib().svo_init_undistort_rectify_map(_p(K, _f64p), _p(d, _f64p), _p(R, _f64p), _p(newK, _f64p), int(w),
+                                              int(h), _p(map1, _i16p), _p(map2, _u16p))
+    if rc != 0:
+        raise SvoError(f"svo_init_undistort_rectify_map: error {rc} (sizes, or newK R is singular)")
+    return map1, map2
+
+
+class RectMaps:
+    """One camera's rectification maps on the device (svo_rect_maps): the CV_16SC2 /
+    CV_16UC1 pair of cv::initUndistortRectifyMap or cv::convertMaps for a raw_w x raw_h
+    camera; the rectified size is the maps' own."""
+
+    def __init__(self, ctx: "Context", raw_w: int, raw_h: int, map1, map2):
+        map1 = _c(map1, np.int16)
+        map2 = _c(map2, np.uint16)
+        if map1.ndim != 3 or map1.shape[2] != 2 or map2.shape != map1.shape[:2]:
+            raise SvoError("RectMaps: map1 (h, w, 2) int16 and map2 (h, w) uint16")
+        self.ctx, self.raw_w, self.raw_h = ctx, int(raw_w), int(raw_h)
+        self.h, self.w = map2.shape
+        hd = _vp()
+        ctx._check(lib().svo_rect_maps_create(ctx.handle, self.raw_w, self.raw_h, self.w, self.h, _p(map1, _i16p),
+                                              _p(map2, _u16p), C.byref(hd)))
+        self.handle = hd
+        ctx._deps[hd.value] = "maps"
+        _LIVE["maps"].add(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if self.ctx._deps.pop(self.handle.value, None):  # (else the context went first and took it along)
+                lib().svo_rect_maps_destroy(self.ctx.handle, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def remap(ctx: "Context", src, maps: RectMaps) -> np.ndarray:
+    """cv::remap(src, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) of a raw frame
+    ((raw_h, raw_w) grey, or (raw_h, raw_w, 3) BGR: grey taps) through the rectifying
+    kernel -> (h, w) uint8 (svo_remap)."""
+    src = _c(src, np.uint8)
+    bgr = src.ndim == 3
+    if src.shape != (maps.raw_h, maps.raw_w) + ((3,) if bgr else ()):
+        raise SvoError(f"remap: a raw frame of {maps.raw_h} x {maps.raw_w} expected, got {src.shape}")
+    out = np.empty((maps.h, maps.w), np.uint8)
+    ctx._check(lib().svo_remap(ctx.handle, _p(src, _u8p), src.shape[1] * (3 if bgr else 1), int(bgr), maps.handle,
+                               _p(out, _u8p), maps.w))
+    return out
 
 
 class OrbParams(C.Structure):
@@ -371,10 +462,12 @@ class Context:
     def close(self):
         if getattr(self, "handle", None):
             L = lib()
-            for kind in ("frontend", "image"):  # dependants still alive go first
+            for kind in ("frontend", "image", "maps"):  # dependants still alive go first (maps outlive front ends)
                 for h in [h for h, k in self._deps.items() if k == kind]:
                     if kind == "frontend":
                         L.svo_frontend_destroy(_vp(h))
+                    elif kind == "maps":
+                        L.svo_rect_maps_destroy(self.handle, _vp(h))
                     else:
                         L.svo_image_destroy(self.handle, _vp(h))
                     del self._deps[h]
@@ -838,14 +931,32 @@ class Frontend:
         self.handle = h
         ctx._deps[h.value] = "frontend"
         self._queued = {}  # ring slot -> (t, lefts, rights) of queue_frames, until upload_wait(t)
+        self._rect = None  # (left, right) RectMaps once set_rectification was called: kept alive, the raw size
         _LIVE["frontend"].add(self)
 
+    def _frame_hw(self):
+        """(rows, columns) of the frames set_frame / queue_frames take: the raw size once
+        rectification is set, else the config's."""
+        if self._rect is not None:
+            return (self._rect[0].raw_h, self._rect[0].raw_w)
+        return (self.cfg.height, self.cfg.width)
+
+    def set_rectification(self, left: RectMaps, right: RectMaps):
+        """svo_frontend_set_rectification: from here on set_frame and queue_frames take
+        the cameras' raw frames and rectify them on the device with each eye's maps.
+        Once, before the first set_frame, queue_frames or init."""
+        self.ctx._check(lib().svo_frontend_set_rectification(self.handle, left.handle, right.handle))
+        self._rect = (left, right)
+
     def set_frame(self, seq, t, left, right):
-        """Stereo pair t of sequence seq: (h, w) grey, or (h, w, 3) BGR converted on the device."""
+        """Stereo pair t of sequence seq: (h, w) grey, or (h, w, 3) BGR converted on the
+        device; raw frames of the maps' raw size once rectification is set."""
         left = _c(left, np.uint8)
         right = _c(right, np.uint8)
         if left.shape != right.shape:
             raise SvoError("set_frame: left / right shapes differ")
+        if self._rect is not None and left.shape[:2] != self._frame_hw():
+            raise SvoError(f"set_frame: raw frames of {self._frame_hw()} expected, got {left.shape}")
         if left.ndim == 3:
             self.ctx._check(lib().svo_frontend_set_frame_bgr(self.handle, seq, t, _p(left, _u8p), _p(right, _u8p),
                                                              3 * left.shape[1]))
@@ -868,7 +979,7 @@ class Frontend:
         if len(lefts) != S or len(rights) != S:
             raise SvoError("queue_frames: one left and one right image per sequence")
         a0 = lefts[0]
-        hw = (self.cfg.height, self.cfg.width)
+        hw = self._frame_hw()  # (the raw size once rectification is set)
         if a0.shape not in (hw, hw + (3,)):
             raise SvoError(f"queue_frames: images must be {hw} grey or {hw + (3,)} BGR, got {a0.shape}")
         bgr = a0.ndim == 3
@@ -980,6 +1091,15 @@ class Frontend:
         """ms per pyramid + Scharr launch chain of frame t, timed alone."""
         ms = np.zeros(1)
         self.ctx._check(lib().svo_frontend_time_pyramid(self.handle, int(t), int(reps), _p(ms, _f64p)))
+        return float(ms[0])
+
+    def time_ingest(self, t, rectify, reps=20):
+        """ms per level-0 write of the left eye (every sequence) from the staging block of
+        the last queue_frames, timed alone: the rectifying kernel (rectify=True) or the
+        plain copy / conversion kernel (svo_frontend_time_ingest)."""
+        ms = np.zeros(1)
+        self.ctx._check(lib().svo_frontend_time_ingest(self.handle, int(t), int(bool(rectify)), int(reps),
+                                                       _p(ms, _f64p)))
         return float(ms[0])
 
     def time_fast(self, t, reps=20):

@@ -235,6 +235,59 @@ int svo_image_upload_bgr(svo_ctx* ctx, svo_image* img, const uint8_t* bgr, int s
     return svo_image_build_pyramid(ctx, img);
 }
 
+// A raw host frame into scratch slot 13 (a descriptor slot, then the frame's bytes
+// up to the end of its last row) and the rectifying kernel from there into level
+// 0 of `img` (device rows), on ctx->stream.
+static int rectify_from_host(svo_ctx* ctx, const uint8_t* raw, int stride, int bgr, const svo_rect_maps* maps,
+                             const svo_image* img) {
+    const RectMapsDev& m = maps->dev;
+    const size_t bytes = (size_t)(m.raw_h - 1) * stride + (size_t)(bgr ? 3 : 1) * m.raw_w;
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slot's last user is done
+    char* d = (char*)scratch(ctx, 13, 256 + bytes);
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "rectify: scratch alloc failed");
+    static_assert(sizeof(PyrDesc) <= 256, "descriptor slot");
+    const PyrDesc* dd = stage_desc(ctx, img, d);
+    if (!dd) return set_error(ctx, SVO_ERR_HIP, "rectify: descriptor staging failed");
+    SVO_HIP(ctx, hipMemcpyAsync(d + 256, raw, bytes, hipMemcpyHostToDevice, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `raw` is the caller's again
+    SVO_HIP(ctx, launch_rectify_batched((const uint8_t*)d + 256, 0, stride, m, dd, 1, bgr != 0, ctx->stream));
+    return SVO_OK;
+}
+
+int svo_image_upload_raw(svo_ctx* ctx, svo_image* img, const uint8_t* raw, int stride, int bgr,
+                         const svo_rect_maps* maps) {
+    if (!ctx || !img || !raw || !maps || stride < (bgr ? 3 : 1) * maps->dev.raw_w)
+        return set_error(ctx, SVO_ERR_ARG, "svo_image_upload_raw: bad arguments");
+    if (img->w != maps->dev.w || img->h != maps->dev.h)
+        return set_error(ctx, SVO_ERR_ARG, "svo_image_upload_raw: the image is not the maps' %d x %d", maps->dev.w,
+                         maps->dev.h);
+    int rc = rectify_from_host(ctx, raw, stride, bgr, maps, img);
+    if (rc) return rc;
+    return svo_image_build_pyramid(ctx, img);
+}
+
+int svo_remap(svo_ctx* ctx, const uint8_t* src, int stride, int bgr, const svo_rect_maps* maps, uint8_t* dst,
+              int dst_stride) {
+    if (!ctx || !src || !maps || !dst || stride < (bgr ? 3 : 1) * maps->dev.raw_w || dst_stride < maps->dev.w)
+        return set_error(ctx, SVO_ERR_ARG, "svo_remap: bad arguments");
+    const int w = maps->dev.w, h = maps->dev.h;
+    // device rows like a level 0's: 64-byte aligned (one dword store per quad)
+    svo_image out;
+    out.w = w;
+    out.h = h;
+    out.nlevels = out.desc.nlevels = 1;
+    const int pitch = (w + 63) & ~63;
+    uint8_t* d = nullptr;
+    SVO_HIP(ctx, hipMalloc((void**)&d, (size_t)pitch * h));
+    out.desc.lv[0] = ImgLevel{d, w, h, pitch};
+    int rc = rectify_from_host(ctx, src, stride, bgr, maps, &out);
+    if (!rc && hipMemcpy2DAsync(dst, dst_stride, d, pitch, w, h, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = set_error(ctx, SVO_ERR_HIP, "svo_remap: D2H copy");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = set_error(ctx, SVO_ERR_HIP, "svo_remap: kernel");
+    (void)hipFree(d);
+    return rc;
+}
+
 int svo_image_level_size(const svo_image* img, int level, int* w, int* h) {
     if (!img || level < 0 || level >= img->nlevels) return SVO_ERR_ARG;
     if (w) *w = img->desc.lv[level].w;

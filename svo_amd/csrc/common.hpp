@@ -46,7 +46,20 @@ inline int lk_levels_for_window(int w, int h, int win_w, int win_h, int max_leve
     return max_level;
 }
 
+// One camera's rectification maps on the device (svo_rect_maps): map1 int16
+// (sx, sy) and map2 uint16 (a | b << 5) per output pixel, rows w apart.
+struct RectMapsDev {
+    const int16_t* map1;
+    const uint16_t* map2;
+    int raw_w, raw_h, w, h;
+};
+
 }  // namespace svo
+
+struct svo_rect_maps {
+    svo::RectMapsDev dev{};
+    void* mem = nullptr;  // one allocation: map1, then map2
+};
 
 struct svo_image {
     int w = 0, h = 0;
@@ -67,7 +80,7 @@ struct svo_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     int64_t lk_iters = 0;
-    svo_scratch s[13];
+    svo_scratch s[14];
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // colour ingest: pinned double buffer (host copy of frame k+1 overlaps the
@@ -103,6 +116,10 @@ int ingest_bgr(svo_ctx* ctx, const uint8_t* bgr, int stride, int w, int h, uint8
 // (grey bytes, or BGR converted as launch_bgr_to_gray)
 hipError_t launch_ingest_batched(const uint8_t* stage, size_t seq_stride, int spitch, const PyrDesc* descs, int S,
                                  int w, int h, bool bgr, hipStream_t st);
+// level 0 (m.w x m.h) of S sequences rectified from a staging block [S][raw_h][spitch]
+// of raw frames (grey bytes or BGR): cv::remap with the fixed-point maps m (rectify.hip)
+hipError_t launch_rectify_batched(const uint8_t* stage, size_t seq_stride, int spitch, const RectMapsDev& m,
+                                  const PyrDesc* descs, int S, bool bgr, hipStream_t st);
 hipError_t launch_pyramid_batched(const PyrDesc* d_descs, int nseq, int w, int h, int nlevels,
                                   hipStream_t st);
 

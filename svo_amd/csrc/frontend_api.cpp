@@ -362,6 +362,30 @@ int svo_frontend_time_pyramid(svo_frontend* fe, int t, int reps, double* ms_per_
     return SVO_OK;
 }
 
+int svo_frontend_time_ingest(svo_frontend* fe, int t, int rectify, int reps, double* ms_per_launch) {
+    if (!fe || t < 0 || reps <= 0 || !ms_per_launch) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    const FeUpload& up = fe->up;
+    if (!up.stage || !up.stride) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_time_ingest: no frames were queued");
+    if (rectify && !fe->rect[0]) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_time_ingest: no rectification set");
+    if (!rectify && (fe->raw_w < fe->W || fe->raw_h < fe->H))
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_time_ingest: the staged frames are smaller than the config's");
+    int rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    SVO_HIP(ctx, hipStreamSynchronize(up.st));
+    const int S = fe->S;
+    const PyrDesc* d = fe->d_desc + (size_t)(t % fe->T) * S;
+    rc = fe_time_launches(ctx, reps, ms_per_launch, [&]() {
+        return rectify ? launch_rectify_batched(up.stage, up.seq, up.stride, fe->rect[0]->dev, d, S, up.bgr != 0,
+                                                ctx->stream)
+                       : launch_ingest_batched(up.stage, up.seq, up.stride, d, S, fe->W, fe->H, up.bgr != 0,
+                                               ctx->stream);
+    });
+    if (rc) return rc;
+    fe->ahead.forget_slot(t % fe->T, fe->T);  // the slot's level 0 was rewritten
+    return SVO_OK;
+}
+
 int svo_frontend_time_fast(svo_frontend* fe, int t, int reps, double* ms_per_launch) {
     if (!fe || t < 0 || reps <= 0 || !ms_per_launch) return SVO_ERR_ARG;
     int rc = svo_frontend_synchronize(fe);

@@ -354,9 +354,11 @@ int fe_drain(svo_frontend* fe) {
 }
 
 int fe_set_frame(svo_frontend* fe, int seq, int t, const uint8_t* left, const uint8_t* right, int stride, bool bgr) {
-    if (!fe || seq < 0 || seq >= fe->S || t < 0 || t >= fe->T || !left || !right || stride < (bgr ? 3 : 1) * fe->W)
+    if (!fe || seq < 0 || seq >= fe->S || t < 0 || t >= fe->T || !left || !right ||
+        stride < (bgr ? 3 : 1) * fe->raw_w)
         return SVO_ERR_ARG;
     svo_ctx* ctx = fe->ctx;
+    fe->fed = true;
     int rd = fe_drain(fe);
     if (rd) return rd;
     fe->ahead.forget_slot(t, fe->T);  // built from / detected on the old image
@@ -365,6 +367,26 @@ int fe_set_frame(svo_frontend* fe, int seq, int t, const uint8_t* left, const ui
     if (!fe->up.t.empty()) {
         fe->up.t[t] = t;
         fe->up.free_rec[t] = 0;
+    }
+    if (fe->rect[0]) {
+        // raw frames: each eye's bytes into the staging pair, rectified from there into
+        // the slot's level 0 with that eye's maps (raw frames are not kept)
+        const size_t bytes = (size_t)(fe->raw_h - 1) * stride + (size_t)(bgr ? 3 : 1) * fe->raw_w;
+        if (bytes > fe->rect_cap) {
+            if (fe->rect_stage) SVO_HIP(ctx, hipFree(fe->rect_stage));
+            fe->rect_stage = nullptr;
+            fe->rect_cap = 0;
+            SVO_HIP(ctx, hipMalloc((void**)&fe->rect_stage, 2 * bytes));
+            fe->rect_cap = bytes;
+        }
+        for (int side = 0; side < 2; side++) {
+            uint8_t* dst = fe->rect_stage + (size_t)side * fe->rect_cap;
+            SVO_HIP(ctx, hipMemcpyAsync(dst, side ? right : left, bytes, hipMemcpyHostToDevice, ctx->stream));
+            const PyrDesc* d = (side ? fe->d_desc_r : fe->d_desc) + (size_t)t * fe->S + seq;
+            SVO_HIP(ctx, launch_rectify_batched(dst, 0, stride, fe->rect[side]->dev, d, 1, bgr, ctx->stream));
+        }
+        SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return SVO_OK;
     }
     for (int side = 0; side < 2; side++) {
         svo_image* im = (side ? fe->frames_r : fe->frames)[(size_t)seq * fe->T + t];
@@ -404,6 +426,8 @@ int svo_frontend_create(svo_ctx* ctx, const svo_frontend_config* cfg, svo_fronte
     fe->cfg = c;
     fe->sw = fe_read_switches(c);
     create_sizes(fe);
+    fe->raw_w = fe->W;
+    fe->raw_h = fe->H;
     for (auto part : {create_frames, create_device_state, create_pinned_mirrors, create_coherent,
                       create_deriv_pyramids, create_loop_state}) {
         int rc = part(fe);
@@ -442,6 +466,7 @@ void svo_frontend_destroy(svo_frontend* fe) {
     for (hipEvent_t e : fe->up.ev_free)
         if (e) (void)hipEventDestroy(e);
     if (fe->up.stage) (void)hipFree(fe->up.stage);
+    if (fe->rect_stage) (void)hipFree(fe->rect_stage);
     orb_batch_destroy(fe->orb);
     if (fe->fit_work) (void)hipFree(fe->fit_work);
     if (fe->win.mem) (void)hipFree(fe->win.mem);
@@ -458,15 +483,36 @@ int svo_frontend_set_frame_bgr(svo_frontend* fe, int seq, int t, const uint8_t* 
     return fe_set_frame(fe, seq, t, left_bgr, right_bgr, stride, true);
 }
 
+int svo_frontend_set_rectification(svo_frontend* fe, const svo_rect_maps* left, const svo_rect_maps* right) {
+    if (!fe || !left || !right) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (fe->fed || fe->rect[0])
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_rectification: once, before the first set_frame, "
+                                           "queue_frames or init");
+    for (const svo_rect_maps* m : {left, right})
+        if (m->dev.w != fe->W || m->dev.h != fe->H)
+            return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_rectification: maps of %d x %d, config %d x %d",
+                             m->dev.w, m->dev.h, fe->W, fe->H);
+    if (left->dev.raw_w != right->dev.raw_w || left->dev.raw_h != right->dev.raw_h)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_rectification: the eyes' raw sizes differ");
+    fe->rect[0] = left;
+    fe->rect[1] = right;
+    fe->raw_w = left->dev.raw_w;
+    fe->raw_h = left->dev.raw_h;
+    return SVO_OK;
+}
+
 int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* left, const uint8_t* const* right,
                               int stride, int bgr) {
-    if (!fe || t < 0 || !left || !right || stride < (bgr ? 3 : 1) * fe->W) return SVO_ERR_ARG;
+    if (!fe || t < 0 || !left || !right || stride < (bgr ? 3 : 1) * fe->raw_w) return SVO_ERR_ARG;
     svo_ctx* ctx = fe->ctx;
     FeUpload& up = fe->up;
-    const int S = fe->S, T = fe->T, W = fe->W, H = fe->H;
+    // (W x H: the host frames' size -- the raw frames' once rectification is set)
+    const int S = fe->S, T = fe->T, W = fe->raw_w, H = fe->raw_h;
     if (T < 4) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_queue_frames: needs a ring of n_frames >= 4");
     for (int s = 0; s < S; s++)
         if (!left[s] || !right[s]) return SVO_ERR_ARG;
+    fe->fed = true;
     // ring discipline: frame t's pyramid is built at the end of step t - 2, so it is
     // queued before that step (t >= stepped + 3); its slot's previous frame t - T is
     // no longer read once step t - T + 1 returned (t <= stepped + T - 1)
@@ -505,6 +551,8 @@ int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* lef
         SVO_HIP(ctx, hipMalloc(&up.stage, 2 * (size_t)S * up.cap));
     }
     up.seq = seq_bytes;  // (the conversion of earlier queued frames captured their own stride)
+    up.stride = stride;
+    up.bgr = bgr != 0;
     const int slot = t % T;
     const size_t last_row = (size_t)(bgr ? 3 : 1) * W;  // bytes of a frame's last row (no stride padding after it)
     // the slot's previous frame (t - T) is last read by LK(t - T + 1): the copy into
@@ -522,7 +570,10 @@ int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* lef
             s0 = s1;
         }
         const PyrDesc* d = (side ? fe->d_desc_r : fe->d_desc) + (size_t)slot * S;
-        SVO_HIP(ctx, launch_ingest_batched(dst, up.seq, stride, d, S, W, H, bgr != 0, up.st));
+        if (fe->rect[side])  // raw frames: the same stage with the eye's gather in front
+            SVO_HIP(ctx, launch_rectify_batched(dst, up.seq, stride, fe->rect[side]->dev, d, S, bgr != 0, up.st));
+        else
+            SVO_HIP(ctx, launch_ingest_batched(dst, up.seq, stride, d, S, W, H, bgr != 0, up.st));
     }
     SVO_HIP(ctx, hipEventRecord(up.ev[slot], up.st));
     up.t[slot] = t;
@@ -556,6 +607,7 @@ int svo_frontend_prebuild_pyramids(svo_frontend* fe) {
 // Frame t0 is a keyframe under either rule (nextFrame: lastFrameID == 0).
 int svo_frontend_init(svo_frontend* fe, int t0) {
     if (!fe || t0 < 0) return SVO_ERR_ARG;
+    fe->fed = true;
     int rd = fe_drain(fe);
     if (rd) return rd;
     fe->ahead.forget_all();

@@ -101,6 +101,7 @@ struct FeUpload {
                                       // run in order on st, so one block serves every frame)
     size_t cap = 0;                   // staging bytes per sequence (the widest h * stride seen)
     size_t seq = 0;                   // h * stride of the last queued frame (sequence stride in staging)
+    int stride = 0, bgr = 0;          // its row stride and format (svo_frontend_time_ingest)
     std::vector<hipEvent_t> ev;       // [T] conversion of the slot's frame done
     std::vector<int> t;               // [T] frame last streamed into the slot (-1: none)
     std::vector<hipEvent_t> ev_free;  // [T] the slot's frame f read for the last time (after LK(f + 1))
@@ -138,6 +139,14 @@ struct svo_frontend {
     std::vector<svo_image*> frames_r;       // right [s*T + t]
     std::vector<svo::PyrDesc> desc_host;    // [t*S + s]
     std::vector<svo::PyrDesc> desc_r_host;  // [t*S + s]
+    // svo_frontend_set_rectification: the eyes' maps (left, right; null: the frames
+    // arrive rectified) and the size the frames' checks use: the raw frame's, W x H
+    // without maps
+    const svo_rect_maps* rect[2] = {nullptr, nullptr};
+    int raw_w = 0, raw_h = 0;
+    bool fed = false;  // a frame was set or queued, or init ran: too late for set_rectification
+    uint8_t* rect_stage = nullptr;  // set_frame with maps: the raw pair's staging ([2 side][rect_cap])
+    size_t rect_cap = 0;
     // device state (one allocation, in carve order)
     void* dmem = nullptr;
     svo::PyrDesc* d_desc = nullptr;    // [t][s]

@@ -11,13 +11,9 @@
 //
 // Byte-moving kernel, HBM bound: 3 B in + 1 B out per pixel. One thread makes
 // four pixels from three aligned dwords and stores one dword.
-#include "common.hpp"
+#include "ingest_device.hpp"
 
 namespace svo {
-
-__device__ __forceinline__ uint32_t gray_of(uint32_t b, uint32_t g, uint32_t r) {
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
 
 // bgr: packed rows, `bpitch` bytes apart (multiple of 4); dst: level 0 rows.
 __global__ void __launch_bounds__(256) bgr_to_gray_kernel(const uint8_t* __restrict__ bgr, int bpitch,
@@ -60,7 +56,6 @@ hipError_t launch_bgr_to_gray(const uint8_t* bgr, int bpitch, uint8_t* dst, int 
 // 4-byte aligned (1241, 3723 B): unaligned dword loads (global memory allows
 // them). Grid (quads / 256, h, S); each sequence's level 0 from the descriptor
 // array (its borders are the pyramid chain's to write).
-typedef uint32_t u32a1 __attribute__((aligned(1)));
 template <bool BGR>
 __global__ void __launch_bounds__(256) ingest_batched_kernel(const uint8_t* __restrict__ stage, size_t seq_stride,
                                                              int spitch, const PyrDesc* __restrict__ descs, int w,
