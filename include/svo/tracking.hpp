@@ -12,6 +12,7 @@
 #include "svo/frame.hpp"
 #include "svo/map.hpp"
 #include "svo/map_point.hpp"
+#include "svo_gpu.h"
 
 namespace svo {
 
@@ -38,6 +39,10 @@ struct Config {
         float y_threshold = 40;
         int features_to_track = 70;
     } tracking;
+    // findLeftFeaturesInRight as svo_stereo_match_rows (row SAD, rectified pairs)
+    // with these parameters in place of the 11x11 stereo LK; off: the reference's call
+    bool use_stereo_rows = false;
+    svo_stereo_rows_params stereo_rows{5, -1, 128, 80, 0};
     int device = 0;
     bool verbose = true;  // the per-frame printf of startStereo
 };

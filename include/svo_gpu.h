@@ -27,6 +27,9 @@
  *   cv::initUndistortRectifyMap(..., CV_16SC2, ...)              svo_init_undistort_rectify_map
  *   cv::remap(..., INTER_LINEAR, BORDER_CONSTANT, 0)             svo_remap / svo_image_upload_raw /
  *                                                                svo_frontend_set_rectification
+ *   (not in the reference: a row search for findLeftFeaturesInRight, R:src/tracking.cpp:94-152,
+ *   on rectified pairs)                                          svo_stereo_match_rows /
+ *                                                                svo_frontend_set_stereo_matcher
  *
  * Conventions (no exceptions cross this ABI; no torch types):
  *   - Host memory is caller-owned. Device memory is owned by the context.
@@ -218,6 +221,42 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
 /* Gauss-Newton iterations executed by the last LK call, summed over points and
  * levels (the "LK iters/s" metric numerator). */
 int64_t svo_lk_last_iterations(const svo_ctx* ctx);
+
+/* ------------------------------------------------------------ stereo rows
+ * (not in the reference, whose findLeftFeaturesInRight is an 11x11 LK that
+ * recovers disparities up to about 70 px:) "row SAD", the stereo match of a
+ * RECTIFIED pair as a bounded search along the left point's own row. Exact
+ * integer arithmetic up to the sub-pixel step. Per left point (x, y), images L
+ * and R of w x h read at level 0 with its stored REFLECT_101 border:
+ *  1. xi = cvRound(x), yi = cvRound(y) (half to even); outside the image: status 0.
+ *  2. candidates: the integers d in [max(d_min, xi - (w - 1)), min(d_max, xi)]
+ *     (the right centre xi - d stays inside); fewer than 3: status 0.
+ *  3. cost(d) = sum over i, j in [-r, r] of |L[yi+i][xi+j] - R[yi+i][xi-d+j]|.
+ *  4. d* = the smallest d of minimal cost; the first or last candidate: status 0.
+ *  5. max_cost > 0 and cost(d*) > max_cost: status 0.
+ *  6. uniq_pct > 0: with second = the least cost over candidates |d - d*| >= 2
+ *     (if there is one), status 0 unless cost(d*) * 100 < uniq_pct * second.
+ *  7. c-, c0, c+ = the costs at d* - 1, d*, d* + 1; den = c- + c+ - 2 c0 (>= 0);
+ *     delta = 0 if den == 0, else float(c- - c+) / float(2 den) (one float32
+ *     division); xr = x - (float(d*) + delta) in float32; yr = y.
+ *  8. next_xy = (xr, yr) with status 1, (x, y) with status 0; disparity = d* and
+ *     cost = c0, both 0 with status 0.
+ * SVO_ERR_ARG (nothing written): radius outside 1..7, d_min < -16, d_max > 255,
+ * d_max - d_min + 1 outside 3..256, uniq_pct outside 0..100, max_cost < 0. */
+typedef struct svo_stereo_rows_params {
+    int radius;   /* patch (2 radius + 1)^2; default 5 */
+    int d_min;    /* lowest disparity searched; default -1 */
+    int d_max;    /* highest disparity searched; default 128 */
+    int uniq_pct; /* uniqueness test in percent, 0 = off; default 80 */
+    int max_cost; /* reject a best cost above this, 0 = off; default 0 */
+} svo_stereo_rows_params;
+/* left / right: images of equal size whose level 0 is uploaded (any upload call
+ * writes the border). n = 0 is valid. disparity / cost (n ints each) may be NULL.
+ * SVO_ERR_ARG (nothing written) in addition: a null ctx, image, params, pts_xy,
+ * next_xy or status (n > 0), n < 0, sizes that differ. */
+int svo_stereo_match_rows(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy, int n,
+                          const svo_stereo_rows_params* params, float* next_xy, uint8_t* status, int* disparity,
+                          int* cost);
 
 /* ------------------------------------------------------------ PnP
  * Batched reprojection residual: M hypotheses (R row-major 3x3, t 3: 12
@@ -483,6 +522,7 @@ typedef struct svo_frontend_config {
     float P_left[12];       /* mProjectionMatrixLeft (KITTI calib P2, R:src/main.cpp:25-28), row-major 3x4 */
     float P_right[12];      /* mProjectionMatrixRight (P3, :29-32) */
     float y_threshold;      /* R:configs/config.yaml:16 -> 40 */
+    /* (the next four are ignored once svo_frontend_set_stereo_matcher is called) */
     int stereo_win;         /* R:src/tracking.cpp:104 -> 11 */
     int stereo_max_level;   /* -> 3 */
     int stereo_max_count;   /* :97 -> 30 */
@@ -551,6 +591,17 @@ int svo_frontend_set_frame_bgr(svo_frontend* fe, int seq, int t, const uint8_t* 
  * later or twice, maps whose w x h is not the config's, eyes of different raw
  * sizes, null arguments. */
 int svo_frontend_set_rectification(svo_frontend* fe, const svo_rect_maps* left, const svo_rect_maps* right);
+/* Row SAD as the keyframe's stereo match: from this call on every stereo match of
+ * the front end (the speculative one and the serial keyframe's) is
+ * svo_stereo_match_rows' rule with these parameters in place of the stereo LK, on
+ * the same stream behind the same events, into the same buffers. The frames must
+ * be rectified (a match is looked for on the left point's row only; y_threshold
+ * always passes). stereo_win, stereo_max_level, stereo_max_count and
+ * stereo_epsilon of the configuration are ignored while the matcher is set.
+ * Nothing else changes; a front end that never calls this launches exactly what
+ * it did. Once, before the first set_frame, queue_frames or init. SVO_ERR_ARG:
+ * called later or twice, null arguments, parameters svo_stereo_match_rows rejects. */
+int svo_frontend_set_stereo_matcher(svo_frontend* fe, const svo_stereo_rows_params* params);
 /* Streamed frames (R:include/async_image_loader.h:36-69: the loader hands each
  * stereo pair to Tracking as it arrives; here a whole step's worth at once):
  * queue frame t of every sequence -- left[s] / right[s] (grey, or BGR 8UC3 when

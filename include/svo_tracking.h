@@ -13,6 +13,8 @@
 
 #include <stdint.h>
 
+#include "svo_gpu.h" /* svo_stereo_rows_params */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -45,6 +47,12 @@ int svo_tracking_push_stereo(svo_tracking* tr, const uint8_t* left, const uint8_
  * cvtColor(COLOR_BGR2GRAY) runs on the device as the frame is uploaded. */
 int svo_tracking_push_stereo_bgr(svo_tracking* tr, const uint8_t* left, const uint8_t* right, int w, int h,
                                  int stride);
+/* findLeftFeaturesInRight as svo_stereo_match_rows (include/svo_gpu.h: row SAD,
+ * rectified pairs) with these parameters in place of the 11x11 stereo LK; the
+ * trace fields stereo_right / stereo_status then carry the matcher's output.
+ * Once, before the first step; -1 when called later or twice, on null arguments
+ * or parameters svo_stereo_match_rows rejects. */
+int svo_tracking_set_stereo_matcher(svo_tracking* tr, const svo_stereo_rows_params* params);
 /* First call: the initial keyframe (extractFeatures + triangulateNewMapPoints);
  * later calls: one iteration of startStereo's loop. Returns 1 if a frame was
  * processed, 0 if no frame was queued, < 0 on error (message in last_error). */

@@ -35,7 +35,7 @@ __all__ = [
     "SvoError", "lib", "Context", "Image", "FastFeatureDetector",
     "TERM_COUNT", "TERM_EPS", "LK_USE_INITIAL_FLOW", "LK_GET_MIN_EIGENVALS", "LK_OPENCV_ORDER",
     "lib_path", "Frontend", "FrontendConfig", "FrontendStats",
-    "RectMaps", "init_undistort_rectify_map", "remap",
+    "RectMaps", "init_undistort_rectify_map", "remap", "StereoRowsParams",
 ]
 
 TERM_COUNT = 1
@@ -125,6 +125,8 @@ _SIGS = [
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_double, C.c_int, C.c_double]),
     ("svo_lk_last_iterations", C.c_int64, [_vp]),
+    ("svo_stereo_match_rows", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, _vp, _f32p, _u8p, _i32p, _i32p]),
+    ("svo_frontend_set_stereo_matcher", C.c_int, [_vp, _vp]),
     ("svo_pnp_residuals", C.c_int, [_vp, _f32p, _f32p, C.c_int, _f64p, C.c_int, _f64p, C.c_float,
                                     _f32p, _u8p, _i32p]),
     ("svo_solve_pnp_ransac", C.c_int, [_vp, _f64p, _f32p, C.c_int, _f64p, C.c_int, C.c_float,
@@ -440,6 +442,18 @@ class OrbParams(C.Structure):
         self.patch_size, self.fast_threshold = patch_size, fast_threshold
 
 
+class StereoRowsParams(C.Structure):
+    """svo_stereo_rows_params: row SAD, the stereo match of a rectified pair as a
+    bounded search along the left point's row (include/svo_gpu.h has the rule).
+    radius 1..7 (patch (2r+1)^2), disparities d_min (>= -16) .. d_max (<= 255), at
+    most 256 of them, uniq_pct 0..100 (0 = off), max_cost >= 0 (0 = off)."""
+    _fields_ = [("radius", C.c_int), ("d_min", C.c_int), ("d_max", C.c_int), ("uniq_pct", C.c_int),
+                ("max_cost", C.c_int)]
+
+    def __init__(self, radius=5, d_min=-1, d_max=128, uniq_pct=80, max_cost=0):
+        super().__init__(int(radius), int(d_min), int(d_max), int(uniq_pct), int(max_cost))
+
+
 class Context:
     """One HIP device + stream (svo_ctx)."""
 
@@ -607,6 +621,23 @@ class Context:
 
     def lk_last_iterations(self) -> int:
         return int(lib().svo_lk_last_iterations(self.handle))
+
+    # ---------------------------------------------------------------- stereo rows
+    def stereo_match_rows(self, left: Image, right: Image, pts, params: "StereoRowsParams" = None,
+                          want_cost: bool = False):
+        """svo_stereo_match_rows on a rectified pair -> (next_pts (n, 2) f32, status (n,)
+        u8), and with want_cost also (disparity (n,) i32, cost (n,) i32)."""
+        params = params or StereoRowsParams()
+        pts = _c(pts, np.float32).reshape(-1, 2)
+        n = len(pts)
+        nxt = np.zeros((n, 2), np.float32)
+        status = np.zeros(n, np.uint8)
+        disp = np.zeros(n, np.int32) if want_cost else None
+        cost = np.zeros(n, np.int32) if want_cost else None
+        self._check(lib().svo_stereo_match_rows(
+            self.handle, left.handle, right.handle, _p(pts, _f32p), n, C.byref(params), _p(nxt, _f32p),
+            _p(status, _u8p), _p(disp, _i32p) if want_cost else None, _p(cost, _i32p) if want_cost else None))
+        return (nxt, status, disp, cost) if want_cost else (nxt, status)
 
     # ---------------------------------------------------------------- PnP
     def pnp_residuals(self, obj, img_pts, hyps, K, thresh2: float = 64.0, want_err: bool = True):
@@ -947,6 +978,15 @@ class Frontend:
         Once, before the first set_frame, queue_frames or init."""
         self.ctx._check(lib().svo_frontend_set_rectification(self.handle, left.handle, right.handle))
         self._rect = (left, right)
+
+    def set_stereo_matcher(self, params: "StereoRowsParams" = None):
+        """svo_frontend_set_stereo_matcher: every stereo match of the front end is row
+        SAD (Context.stereo_match_rows' rule) with `params` instead of the stereo LK;
+        the frames must be rectified. Once, before the first set_frame, queue_frames
+        or init."""
+        params = params or StereoRowsParams()
+        self.ctx._check(lib().svo_frontend_set_stereo_matcher(self.handle, C.byref(params)))
+        self._rows = params
 
     def set_frame(self, seq, t, left, right):
         """Stereo pair t of sequence seq: (h, w) grey, or (h, w, 3) BGR converted on the

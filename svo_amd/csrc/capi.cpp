@@ -537,6 +537,42 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
 
 int64_t svo_lk_last_iterations(const svo_ctx* ctx) { return ctx ? ctx->lk_iters : 0; }
 
+// ------------------------------------------------------------------ stereo rows
+int svo_stereo_match_rows(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy, int n,
+                          const svo_stereo_rows_params* params, float* next_xy, uint8_t* status, int* disparity,
+                          int* cost) {
+    if (!ctx || !left || !right || !params) return SVO_ERR_ARG;
+    if (n < 0 || (n > 0 && (!pts_xy || !next_xy || !status)))
+        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: bad arguments");
+    if (left->w != right->w || left->h != right->h)
+        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: image sizes differ");
+    if (!stereo_rows_params_ok(*params))
+        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: parameters out of range (radius 1..7, d_min >= -16, "
+                                           "d_max <= 255, 3..256 disparities, uniq_pct 0..100, max_cost >= 0)");
+    if (n == 0) return SVO_OK;
+    const size_t N = (size_t)n;
+    char* d = (char*)scratch(ctx, 7, 512 + N * (8 + 8 + 4 + 4 + 1));
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    static_assert(sizeof(PyrDesc) <= 256, "descriptor slot");
+    float* dpts = (float*)(d + 512);
+    float* dnext = dpts + 2 * N;
+    int* ddisp = (int*)(dnext + 2 * N);
+    int* dcost = ddisp + N;
+    uint8_t* dst = (uint8_t*)(dcost + N);
+    const PyrDesc* dl = stage_desc(ctx, left, d);
+    const PyrDesc* dr = dl ? stage_desc(ctx, right, d + 256) : nullptr;
+    if (!dl || !dr) return set_error(ctx, SVO_ERR_HIP, "desc staging");
+    SVO_HIP(ctx, hipMemcpyAsync(dpts, pts_xy, sizeof(float) * 2 * N, hipMemcpyHostToDevice, ctx->stream));
+    StereoRowsBatch b{dl, dr, dpts, dnext, dst, disparity ? ddisp : nullptr, cost ? dcost : nullptr, nullptr, n, n};
+    SVO_HIP(ctx, launch_stereo_rows(b, 1, n, *params, ctx->stream));
+    SVO_HIP(ctx, hipMemcpyAsync(next_xy, dnext, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(ctx, hipMemcpyAsync(status, dst, N, hipMemcpyDeviceToHost, ctx->stream));
+    if (disparity) SVO_HIP(ctx, hipMemcpyAsync(disparity, ddisp, sizeof(int) * N, hipMemcpyDeviceToHost, ctx->stream));
+    if (cost) SVO_HIP(ctx, hipMemcpyAsync(cost, dcost, sizeof(int) * N, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
 // ------------------------------------------------------------------ PnP residuals
 int svo_pnp_residuals(svo_ctx* ctx, const float* obj_xyz, const float* img_xy, int n,
                       const double* hyp_Rt, int m, const double K[9], float thresh2, float* err,

@@ -252,6 +252,28 @@ struct LKBatch {
 hipError_t launch_lk(const LKBatch& b, int nseq, int max_n, const LKParams& p, hipStream_t st);
 bool lk_supported(int win_w, int win_h);
 
+// Batched row SAD (stereo_rows.hip; the rule: svo_stereo_match_rows): the stereo
+// match of rectified pairs. LKBatch's shape, so it stands where launch_lk stands
+// for the stereo call: sequence s (blockIdx.y) reads level 0 of left[s] / right[s]
+// and owns points [s*cap, s*cap + n_s) of every array, n_s = counts[s] (device)
+// or n when counts is null; grid_hint as LKBatch's.
+struct StereoRowsBatch {
+    const PyrDesc* left;   // [nseq] device
+    const PyrDesc* right;  // [nseq] device
+    const float* prev_xy;
+    float* next_xy;
+    uint8_t* status;
+    int* disparity;  // nullable
+    int* cost;       // nullable
+    const int* counts;  // nullable
+    int n, cap;
+    int grid_hint = 0;
+};
+bool stereo_rows_params_ok(const svo_stereo_rows_params& p);
+// hipErrorInvalidValue (nothing launched) for parameters stereo_rows_params_ok rejects
+hipError_t launch_stereo_rows(const StereoRowsBatch& b, int nseq, int max_n, const svo_stereo_rows_params& p,
+                              hipStream_t st);
+
 // Batched residual scoring: blockIdx.z = sequence, blockIdx.y = hypothesis.
 // Sequence s: obj/img points [s*cap, s*cap + n_s), hypotheses [s*m, s*m + m),
 // err rows of cap floats, bits rows of words_cap words, cnt per hypothesis.

@@ -85,6 +85,8 @@ static int fe_queue_pre(svo_frontend* fe, int tn) {
 // findLeftFeaturesInRight: calcOpticalFlowPyrLK(left, right, pts, 11x11, 3,
 // {COUNT+EPS, 30, 0.001}), flags 0 (R:src/tracking.cpp:97-105) of st_xy[0,
 // counts[s]) of every sequence of frame t; max_n bounds every count (the grid).
+// With svo_frontend_set_stereo_matcher: row SAD in its place, same wait, same
+// buffers, same phase.
 static int fe_stereo_lk(svo_frontend* fe, int t, const int* counts, int max_n, hipStream_t st, int grid_hint = 0) {
     svo_ctx* ctx = fe->ctx;
     const svo_frontend_config& c = fe->cfg;
@@ -92,6 +94,14 @@ static int fe_stereo_lk(svo_frontend* fe, int t, const int* counts, int max_n, h
     SVO_HIP(ctx, hipStreamWaitEvent(st, fe->ev_pyr_r_b[t & 1], 0));
     const PyrDesc* dl = fe->d_desc + (size_t)(t % fe->T) * fe->S;
     const PyrDesc* dr = fe->d_desc_r + (size_t)(t % fe->T) * fe->S;
+    if (fe->rows_on) {
+        StereoRowsBatch rb{dl, dr, fe->st_xy, fe->st_next, fe->st_status, nullptr, nullptr, counts, 0, fe->CAP};
+        rb.grid_hint = grid_hint;
+        ph_begin(fe, PH_STEREO, st, &slot);
+        SVO_HIP(ctx, launch_stereo_rows(rb, fe->S, std::min(std::max(max_n, 0), fe->CAP), fe->rows, st));
+        ph_end(fe, st, slot);
+        return SVO_OK;
+    }
     LKBatch lb{dl, dr, fe->d_der + (size_t)(t % 3) * fe->S, fe->st_xy, fe->st_next, fe->st_status, nullptr, nullptr,
                counts, 0, fe->CAP};
     lb.grid_hint = grid_hint;

@@ -502,6 +502,19 @@ int svo_frontend_set_rectification(svo_frontend* fe, const svo_rect_maps* left, 
     return SVO_OK;
 }
 
+int svo_frontend_set_stereo_matcher(svo_frontend* fe, const svo_stereo_rows_params* params) {
+    if (!fe || !params) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (fe->fed || fe->rows_on)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_matcher: once, before the first set_frame, "
+                                           "queue_frames or init");
+    if (!stereo_rows_params_ok(*params))
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_matcher: parameters out of range");
+    fe->rows = *params;
+    fe->rows_on = true;
+    return SVO_OK;
+}
+
 int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* left, const uint8_t* const* right,
                               int stride, int bgr) {
     if (!fe || t < 0 || !left || !right || stride < (bgr ? 3 : 1) * fe->raw_w) return SVO_ERR_ARG;

@@ -144,7 +144,10 @@ struct svo_frontend {
     // without maps
     const svo_rect_maps* rect[2] = {nullptr, nullptr};
     int raw_w = 0, raw_h = 0;
-    bool fed = false;  // a frame was set or queued, or init ran: too late for set_rectification
+    bool fed = false;  // a frame was set or queued, or init ran: too late for set_rectification / set_stereo_matcher
+    // svo_frontend_set_stereo_matcher: row SAD (launch_stereo_rows) in place of the stereo LK
+    bool rows_on = false;
+    svo_stereo_rows_params rows{};
     uint8_t* rect_stage = nullptr;  // set_frame with maps: the raw pair's staging ([2 side][rect_cap])
     size_t rect_cap = 0;
     // device state (one allocation, in carve order)

@@ -155,7 +155,15 @@ void Tracking::findLeftFeaturesInRight(StereoFrame* frame) const {
     std::vector<Point2f> rightPoints(n);
     std::vector<uint8_t> status(n);
     std::vector<float> error(n);
-    if (n > 0 &&
+    if (mConfig.use_stereo_rows) {
+        // (not in the reference) the match on the left point's own row of a rectified pair
+        if (n > 0 && svo_stereo_match_rows(mGpu, frame->leftImg().device(mGpu, kMaxLevel),
+                                           frame->rightImg().device(mGpu, kMaxLevel),
+                                           reinterpret_cast<const float*>(leftPoints.data()), (int)n,
+                                           &mConfig.stereo_rows, reinterpret_cast<float*>(rightPoints.data()),
+                                           status.data(), nullptr, nullptr) != SVO_OK)
+            fail(mGpu, "svo_stereo_match_rows");
+    } else if (n > 0 &&
         svo_calc_optical_flow_pyr_lk(mGpu, frame->leftImg().device(mGpu, kMaxLevel),
                                      frame->rightImg().device(mGpu, kMaxLevel),
                                      reinterpret_cast<const float*>(leftPoints.data()), (int)n,

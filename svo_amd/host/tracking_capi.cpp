@@ -89,6 +89,18 @@ int svo_tracking_push_stereo_bgr(svo_tracking* tr, const uint8_t* left, const ui
     return 0;
 }
 
+int svo_tracking_set_stereo_matcher(svo_tracking* tr, const svo_stereo_rows_params* params) {
+    if (!tr || !params || tr->started || tr->config.use_stereo_rows) return -1;
+    const svo_stereo_rows_params& p = *params;
+    const long span = (long)p.d_max - (long)p.d_min + 1;
+    if (p.radius < 1 || p.radius > 7 || p.d_min < -16 || p.d_max > 255 || span < 3 || span > 256 || p.uniq_pct < 0 ||
+        p.uniq_pct > 100 || p.max_cost < 0)
+        return -1;
+    tr->config.stereo_rows = p;  // (Tracking reads the config by reference)
+    tr->config.use_stereo_rows = true;
+    return 0;
+}
+
 int svo_tracking_step(svo_tracking* tr) {
     if (!tr) return -1;
     try {

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import SvoError, lib as _gpu_lib
+from . import StereoRowsParams, SvoError, lib as _gpu_lib
 
 _LIB = None
 _u8p = C.POINTER(C.c_uint8)
@@ -37,6 +37,7 @@ _SIGS = [
     ("svo_tracking_last_error", C.c_char_p, [_vp]),
     ("svo_tracking_push_stereo", C.c_int, [_vp, _u8p, _u8p, C.c_int, C.c_int, C.c_int]),
     ("svo_tracking_push_stereo_bgr", C.c_int, [_vp, _u8p, _u8p, C.c_int, C.c_int, C.c_int]),
+    ("svo_tracking_set_stereo_matcher", C.c_int, [_vp, _vp]),
     ("svo_tracking_step", C.c_int, [_vp]),
     ("svo_tracking_frame_info", C.c_int, [_vp, _i64p, _i32p, _i64p, _i64p, _f64p, _f64p]),
     ("svo_tracking_features", C.c_int, [_vp, _f32p, _f64p, _i64p, C.c_int, _i32p]),
@@ -124,6 +125,13 @@ class Tracking:
         if lib().svo_tracking_push_stereo_bgr(self.handle, left.ctypes.data_as(_u8p), right.ctypes.data_as(_u8p),
                                               w, h, 3 * w) != 0:
             raise SvoError("svo_tracking_push_stereo_bgr: " + lib().svo_tracking_last_error(self.handle).decode())
+
+    def set_stereo_matcher(self, params: StereoRowsParams = None):
+        """svo_tracking_set_stereo_matcher: findLeftFeaturesInRight as row SAD
+        (svo_stereo_match_rows) instead of the stereo LK. Once, before the first step."""
+        params = params or StereoRowsParams()
+        if lib().svo_tracking_set_stereo_matcher(self.handle, C.byref(params)) != 0:
+            raise SvoError("svo_tracking_set_stereo_matcher: before the first step, once, parameters in range")
 
     def step(self) -> bool:
         rc = lib().svo_tracking_step(self.handle)
