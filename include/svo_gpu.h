@@ -30,6 +30,11 @@
  *   (not in the reference: a row search for findLeftFeaturesInRight, R:src/tracking.cpp:94-152,
  *   on rectified pairs)                                          svo_stereo_match_rows /
  *                                                                svo_frontend_set_stereo_matcher
+ *   (not in the reference: the same search around the feature's
+ *   disparity one frame ago, a right column for every tracked
+ *   feature of every frame of the window)                        svo_stereo_match_rows_guided /
+ *                                                                svo_stereo_row_priors /
+ *                                                                svo_frontend_set_stereo_tracking
  *
  * Conventions (no exceptions cross this ABI; no torch types):
  *   - Host memory is caller-owned. Device memory is owned by the context.
@@ -257,6 +262,33 @@ typedef struct svo_stereo_rows_params {
 int svo_stereo_match_rows(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy, int n,
                           const svo_stereo_rows_params* params, float* next_xy, uint8_t* status, int* disparity,
                           int* cost);
+
+/* Guided row SAD: svo_stereo_match_rows where point i searches its own range
+ * [d_min_i, d_max_i] in place of [d_min, d_max]:
+ *   d_prior[i] == SVO_STEREO_NO_PRIOR: [d_min, d_max];
+ *   otherwise [max(d_min, d_prior[i] - guide), min(d_max, d_prior[i] + guide)],
+ *   evaluated without overflow (every other int is a valid prior).
+ * Steps 1-8 above run with that range and nothing else changes, so: a range that
+ * step 2 leaves fewer than 3 candidates of gives status 0; a best cost at either
+ * end of the guided range gives status 0 (the prior was wrong, or the minimum
+ * lies outside); the uniqueness test sees the guided candidates only.
+ * d_prior == NULL, or guide == 0 with any priors, returns svo_stereo_match_rows'
+ * outputs. SVO_ERR_ARG (nothing written): whatever svo_stereo_match_rows
+ * refuses, guide outside 0..15. */
+#define SVO_STEREO_NO_PRIOR INT32_MIN
+int svo_stereo_match_rows_guided(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy,
+                                 int n, const svo_stereo_rows_params* params, const int* d_prior, int guide,
+                                 float* next_xy, uint8_t* status, int* disparity, int* cost);
+/* The prior of a tracked feature: its disparity one frame ago. Per feature i,
+ * mid[i] is looked up in prev_mid (prev_n ids, strictly increasing, as a window
+ * slot's are); found at j with prev_ur[j] >= 0: d_prior[i] = cvRound(prev_xy[2j] -
+ * prev_ur[j]) (one float32 subtraction, rounded half to even), or
+ * SVO_STEREO_NO_PRIOR where that is not finite or outside +-32767; absent, or
+ * prev_ur[j] < 0, or prev_n == 0: SVO_STEREO_NO_PRIOR. n = 0 is valid.
+ * SVO_ERR_ARG (nothing written): null ctx, n < 0, prev_n < 0, a null array of a
+ * count > 0. */
+int svo_stereo_row_priors(svo_ctx* ctx, const int* mid, int n, const int* prev_mid, const float* prev_xy,
+                          const float* prev_ur, int prev_n, int* d_prior);
 
 /* ------------------------------------------------------------ PnP
  * Batched reprojection residual: M hypotheses (R row-major 3x3, t 3: 12
@@ -680,7 +712,8 @@ int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta
 /* The stereo window: svo_frontend_window_enable, and the ring also keeps one
  * float per feature and slot, the right image's column of the stereo match
  * (findLeftFeaturesInRight's LK) that created the feature, in the frame that
- * created it, and -1 in every later frame that tracks it; the init frame's
+ * created it, and -1 in every later frame that tracks it (unless
+ * svo_frontend_set_stereo_tracking, below, matches it there); the init frame's
  * features all carry theirs. With the plain svo_frontend_window_enable none of
  * this is allocated or written. SVO_ERR_ARG in addition: the configuration's
  * P_right gives no baseline -P_right[3] / P_right[0] > 0. */
@@ -696,6 +729,22 @@ int svo_frontend_window_right(svo_frontend* fe, int seq, int cap, float* ur);
  * svo_frontend_window_right. SVO_ERR_ARG in addition: no stereo window enabled. */
 int svo_frontend_bundle_adjust_stereo(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations,
                                       double* costs, int* iterations, int* sizes);
+/* Stereo columns for tracked features (opt-in; RECTIFIED frames): from this call
+ * on every recorded frame also matches its tracked features -- the first
+ * nA - added of the list the step leaves -- between level 0 of its own left and
+ * right images with svo_stereo_match_rows_guided, and the ring's right column of
+ * a tracked feature is the matched column where the status is 1, -1 otherwise
+ * (the frame's new features keep the column of the match that created them).
+ * The prior is svo_stereo_row_priors against the window's slot of frame t - 1,
+ * if that slot holds frame t - 1 and its epoch is the map's current one;
+ * otherwise (after a map reclaim, a restart) no feature has a prior. guide == 0
+ * skips the lookup: the full range for every feature. Features, poses, map
+ * points, counts and the window's xy / ids are those of a front end that never
+ * made the call, bit for bit; the match runs behind the keyframe beside the
+ * record, off the step's critical path, whichever matcher the keyframe uses.
+ * SVO_ERR_ARG: no stereo window enabled, called after svo_frontend_init or twice,
+ * null arguments, parameters svo_stereo_match_rows rejects, guide outside 0..15. */
+int svo_frontend_set_stereo_tracking(svo_frontend* fe, const svo_stereo_rows_params* params, int guide);
 /* Accumulated per-phase device time (ms) and launch counts since create/reset:
  * phases: 0 pyramid (left + Scharr), 1 lk, 2 post_lk, 3 stereo_lk, 4 pnp_score,
  * 5 tail (keyframe), 6 fast, 7 bucket, 8 append, 9 pyramid_right. Returns the number

@@ -35,8 +35,10 @@ __all__ = [
     "SvoError", "lib", "Context", "Image", "FastFeatureDetector",
     "TERM_COUNT", "TERM_EPS", "LK_USE_INITIAL_FLOW", "LK_GET_MIN_EIGENVALS", "LK_OPENCV_ORDER",
     "lib_path", "Frontend", "FrontendConfig", "FrontendStats",
-    "RectMaps", "init_undistort_rectify_map", "remap", "StereoRowsParams",
+    "RectMaps", "init_undistort_rectify_map", "remap", "StereoRowsParams", "STEREO_NO_PRIOR",
 ]
+
+STEREO_NO_PRIOR = -(2 ** 31)  # SVO_STEREO_NO_PRIOR: a point of the guided row match without a prior
 
 TERM_COUNT = 1
 TERM_EPS = 2
@@ -127,6 +129,10 @@ _SIGS = [
     ("svo_lk_last_iterations", C.c_int64, [_vp]),
     ("svo_stereo_match_rows", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, _vp, _f32p, _u8p, _i32p, _i32p]),
     ("svo_frontend_set_stereo_matcher", C.c_int, [_vp, _vp]),
+    ("svo_stereo_match_rows_guided", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, _vp, _i32p, C.c_int, _f32p, _u8p, _i32p,
+                                               _i32p]),
+    ("svo_stereo_row_priors", C.c_int, [_vp, _i32p, C.c_int, _i32p, _f32p, _f32p, C.c_int, _i32p]),
+    ("svo_frontend_set_stereo_tracking", C.c_int, [_vp, _vp, C.c_int]),
     ("svo_pnp_residuals", C.c_int, [_vp, _f32p, _f32p, C.c_int, _f64p, C.c_int, _f64p, C.c_float,
                                     _f32p, _u8p, _i32p]),
     ("svo_solve_pnp_ransac", C.c_int, [_vp, _f64p, _f32p, C.c_int, _f64p, C.c_int, C.c_float,
@@ -639,6 +645,44 @@ class Context:
             _p(status, _u8p), _p(disp, _i32p) if want_cost else None, _p(cost, _i32p) if want_cost else None))
         return (nxt, status, disp, cost) if want_cost else (nxt, status)
 
+    def stereo_match_rows_guided(self, left: Image, right: Image, pts, d_prior=None, guide: int = 4,
+                                 params: "StereoRowsParams" = None, want_cost: bool = False):
+        """svo_stereo_match_rows_guided: stereo_match_rows where point i searches
+        d_prior[i] +- guide (STEREO_NO_PRIOR: the full range); d_prior None or guide 0
+        is stereo_match_rows itself. Returns what stereo_match_rows returns."""
+        params = params or StereoRowsParams()
+        pts = _c(pts, np.float32).reshape(-1, 2)
+        n = len(pts)
+        if d_prior is not None:
+            d_prior = _c(d_prior, np.int32).reshape(-1)
+            if len(d_prior) != n:
+                raise ValueError("d_prior: one int per point")
+        nxt = np.zeros((n, 2), np.float32)
+        status = np.zeros(n, np.uint8)
+        disp = np.zeros(n, np.int32) if want_cost else None
+        cost = np.zeros(n, np.int32) if want_cost else None
+        self._check(lib().svo_stereo_match_rows_guided(
+            self.handle, left.handle, right.handle, _p(pts, _f32p), n, C.byref(params),
+            _p(d_prior, _i32p) if d_prior is not None else None, int(guide), _p(nxt, _f32p), _p(status, _u8p),
+            _p(disp, _i32p) if want_cost else None, _p(cost, _i32p) if want_cost else None))
+        return (nxt, status, disp, cost) if want_cost else (nxt, status)
+
+    def stereo_row_priors(self, mid, prev_mid, prev_xy, prev_ur):
+        """svo_stereo_row_priors: per feature id in mid its disparity in the previous
+        frame's lists (prev_mid strictly increasing, prev_xy (m, 2), prev_ur (m,)), or
+        STEREO_NO_PRIOR -> (n,) i32."""
+        mid = _c(mid, np.int32).reshape(-1)
+        prev_mid = _c(prev_mid, np.int32).reshape(-1)
+        prev_xy = _c(prev_xy, np.float32).reshape(-1, 2)
+        prev_ur = _c(prev_ur, np.float32).reshape(-1)
+        if not (len(prev_mid) == len(prev_xy) == len(prev_ur)):
+            raise ValueError("prev_mid, prev_xy, prev_ur: one entry per previous feature")
+        out = np.zeros(len(mid), np.int32)
+        self._check(lib().svo_stereo_row_priors(
+            self.handle, _p(mid, _i32p), len(mid), _p(prev_mid, _i32p), _p(prev_xy, _f32p), _p(prev_ur, _f32p),
+            len(prev_mid), _p(out, _i32p)))
+        return out
+
     # ---------------------------------------------------------------- PnP
     def pnp_residuals(self, obj, img_pts, hyps, K, thresh2: float = 64.0, want_err: bool = True):
         """hyps: (m, 12) = R row-major + t. -> (err (m,n) f32, mask (m,n) u8, counts (m,))."""
@@ -987,6 +1031,16 @@ class Frontend:
         params = params or StereoRowsParams()
         self.ctx._check(lib().svo_frontend_set_stereo_matcher(self.handle, C.byref(params)))
         self._rows = params
+
+    def set_stereo_tracking(self, params: "StereoRowsParams" = None, guide: int = 4):
+        """svo_frontend_set_stereo_tracking: every recorded frame matches its tracked
+        features in its own right image (Context.stereo_match_rows_guided around the
+        feature's disparity one frame ago), so the stereo window holds a right column
+        for them too; the frames must be rectified. Once, after
+        window_enable(stereo=True) and before init."""
+        params = params or StereoRowsParams()
+        self.ctx._check(lib().svo_frontend_set_stereo_tracking(self.handle, C.byref(params), int(guide)))
+        self._trk = (params, guide)
 
     def set_frame(self, seq, t, left, right):
         """Stereo pair t of sequence seq: (h, w) grey, or (h, w, 3) BGR converted on the

@@ -538,37 +538,94 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
 int64_t svo_lk_last_iterations(const svo_ctx* ctx) { return ctx ? ctx->lk_iters : 0; }
 
 // ------------------------------------------------------------------ stereo rows
-int svo_stereo_match_rows(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy, int n,
-                          const svo_stereo_rows_params* params, float* next_xy, uint8_t* status, int* disparity,
-                          int* cost) {
+// svo_stereo_match_rows (d_prior null or guide 0: launch_stereo_rows, as ever) and
+// svo_stereo_match_rows_guided
+static int rows_match(svo_ctx* ctx, const char* who, const svo_image* left, const svo_image* right,
+                      const float* pts_xy, int n, const svo_stereo_rows_params* params, const int* d_prior, int guide,
+                      float* next_xy, uint8_t* status, int* disparity, int* cost) {
     if (!ctx || !left || !right || !params) return SVO_ERR_ARG;
     if (n < 0 || (n > 0 && (!pts_xy || !next_xy || !status)))
-        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: bad arguments");
-    if (left->w != right->w || left->h != right->h)
-        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: image sizes differ");
+        return set_error(ctx, SVO_ERR_ARG, "%s: bad arguments", who);
+    if (left->w != right->w || left->h != right->h) return set_error(ctx, SVO_ERR_ARG, "%s: image sizes differ", who);
     if (!stereo_rows_params_ok(*params))
-        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_match_rows: parameters out of range (radius 1..7, d_min >= -16, "
-                                           "d_max <= 255, 3..256 disparities, uniq_pct 0..100, max_cost >= 0)");
+        return set_error(ctx, SVO_ERR_ARG, "%s: parameters out of range (radius 1..7, d_min >= -16, "
+                                           "d_max <= 255, 3..256 disparities, uniq_pct 0..100, max_cost >= 0)", who);
+    if (guide < 0 || guide > 15) return set_error(ctx, SVO_ERR_ARG, "%s: guide outside 0..15", who);
     if (n == 0) return SVO_OK;
+    const bool guided = d_prior && guide > 0;
     const size_t N = (size_t)n;
-    char* d = (char*)scratch(ctx, 7, 512 + N * (8 + 8 + 4 + 4 + 1));
+    char* d = (char*)scratch(ctx, 7, 512 + N * (8 + 8 + 4 + 4 + 4 + 1));
     if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     static_assert(sizeof(PyrDesc) <= 256, "descriptor slot");
     float* dpts = (float*)(d + 512);
     float* dnext = dpts + 2 * N;
     int* ddisp = (int*)(dnext + 2 * N);
     int* dcost = ddisp + N;
-    uint8_t* dst = (uint8_t*)(dcost + N);
+    int* dprior = dcost + N;
+    uint8_t* dst = (uint8_t*)(dprior + N);
     const PyrDesc* dl = stage_desc(ctx, left, d);
     const PyrDesc* dr = dl ? stage_desc(ctx, right, d + 256) : nullptr;
     if (!dl || !dr) return set_error(ctx, SVO_ERR_HIP, "desc staging");
     SVO_HIP(ctx, hipMemcpyAsync(dpts, pts_xy, sizeof(float) * 2 * N, hipMemcpyHostToDevice, ctx->stream));
     StereoRowsBatch b{dl, dr, dpts, dnext, dst, disparity ? ddisp : nullptr, cost ? dcost : nullptr, nullptr, n, n};
-    SVO_HIP(ctx, launch_stereo_rows(b, 1, n, *params, ctx->stream));
+    if (guided) {
+        SVO_HIP(ctx, hipMemcpyAsync(dprior, d_prior, sizeof(int) * N, hipMemcpyHostToDevice, ctx->stream));
+        SVO_HIP(ctx, launch_stereo_rows_guided(b, 1, n, *params, dprior, guide, 0, ctx->stream));
+    } else {
+        SVO_HIP(ctx, launch_stereo_rows(b, 1, n, *params, ctx->stream));
+    }
     SVO_HIP(ctx, hipMemcpyAsync(next_xy, dnext, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(status, dst, N, hipMemcpyDeviceToHost, ctx->stream));
     if (disparity) SVO_HIP(ctx, hipMemcpyAsync(disparity, ddisp, sizeof(int) * N, hipMemcpyDeviceToHost, ctx->stream));
     if (cost) SVO_HIP(ctx, hipMemcpyAsync(cost, dcost, sizeof(int) * N, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
+int svo_stereo_match_rows(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy, int n,
+                          const svo_stereo_rows_params* params, float* next_xy, uint8_t* status, int* disparity,
+                          int* cost) {
+    return rows_match(ctx, "svo_stereo_match_rows", left, right, pts_xy, n, params, nullptr, 0, next_xy, status,
+                      disparity, cost);
+}
+
+int svo_stereo_match_rows_guided(svo_ctx* ctx, const svo_image* left, const svo_image* right, const float* pts_xy,
+                                 int n, const svo_stereo_rows_params* params, const int* d_prior, int guide,
+                                 float* next_xy, uint8_t* status, int* disparity, int* cost) {
+    return rows_match(ctx, "svo_stereo_match_rows_guided", left, right, pts_xy, n, params, d_prior, guide, next_xy,
+                      status, disparity, cost);
+}
+
+int svo_stereo_row_priors(svo_ctx* ctx, const int* mid, int n, const int* prev_mid, const float* prev_xy,
+                          const float* prev_ur, int prev_n, int* d_prior) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (n < 0 || prev_n < 0 || (n > 0 && (!mid || !d_prior)) || (prev_n > 0 && (!prev_mid || !prev_xy || !prev_ur)))
+        return set_error(ctx, SVO_ERR_ARG, "svo_stereo_row_priors: bad arguments");
+    if (n == 0) return SVO_OK;
+    const size_t N = (size_t)n, M = (size_t)prev_n;
+    char* d = (char*)scratch(ctx, 7, 256 + N * 8 + M * 16);
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    int* dmid = (int*)d;
+    int* dout = dmid + N;
+    int* dpm = dout + N;
+    float* dpxy = (float*)(dpm + M);
+    float* dpur = dpxy + 2 * M;
+    SVO_HIP(ctx, hipMemcpyAsync(dmid, mid, sizeof(int) * N, hipMemcpyHostToDevice, ctx->stream));
+    if (M) {
+        SVO_HIP(ctx, hipMemcpyAsync(dpm, prev_mid, sizeof(int) * M, hipMemcpyHostToDevice, ctx->stream));
+        SVO_HIP(ctx, hipMemcpyAsync(dpxy, prev_xy, sizeof(float) * 2 * M, hipMemcpyHostToDevice, ctx->stream));
+        SVO_HIP(ctx, hipMemcpyAsync(dpur, prev_ur, sizeof(float) * M, hipMemcpyHostToDevice, ctx->stream));
+    }
+    RowPriorsBatch b{};
+    b.mid = dmid;
+    b.n = b.cap = n;
+    b.prev_mid = M ? dpm : nullptr;
+    b.prev_xy = dpxy;
+    b.prev_ur = dpur;
+    b.prev_n_host = b.prev_cap = prev_n;
+    b.d_prior = dout;
+    SVO_HIP(ctx, launch_row_priors(b, 1, n, ctx->stream));
+    SVO_HIP(ctx, hipMemcpyAsync(d_prior, dout, sizeof(int) * N, hipMemcpyDeviceToHost, ctx->stream));
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVO_OK;
 }

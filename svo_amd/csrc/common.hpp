@@ -273,6 +273,40 @@ bool stereo_rows_params_ok(const svo_stereo_rows_params& p);
 // hipErrorInvalidValue (nothing launched) for parameters stereo_rows_params_ok rejects
 hipError_t launch_stereo_rows(const StereoRowsBatch& b, int nseq, int max_n, const svo_stereo_rows_params& p,
                               hipStream_t st);
+// Guided row SAD (the rule: svo_stereo_match_rows_guided): point i of sequence s
+// searches d_prior[s*cap + i] +- guide (1..15) cut to the parameters' range, or
+// the full range where d_prior is SVO_STEREO_NO_PRIOR. Two launches: four guided
+// points per wave, then the points without a prior, a wave each on a grid of
+// full_grid blocks per sequence (<= 0: max_n; its waves loop). b.grid_hint is not
+// used. hipErrorInvalidValue (nothing launched) for bad parameters, a null d_prior
+// or a guide outside 1..15 (guide 0 is launch_stereo_rows).
+hipError_t launch_stereo_rows_guided(const StereoRowsBatch& b, int nseq, int max_n, const svo_stereo_rows_params& p,
+                                     const int* d_prior, int guide, int full_grid, hipStream_t st);
+// The priors of svo_stereo_row_priors, batched: sequence s owns features
+// [s*cap, s*cap + n_s) of mid / d_prior, n_s = (counts ? counts[s] : n) -
+// max(sub[s], 0) (sub nullable), written to n_out[s] (nullable); its previous
+// list is prev_*[s*prev_stride ..] of prev_n[s*prev_n_stride] entries (prev_n
+// null: prev_n_host), taken as empty where prev_epoch[s*prev_n_stride] !=
+// cur_epoch[s] (prev_epoch nullable) or prev_mid is null.
+struct RowPriorsBatch {
+    const int* mid;
+    const int* counts;  // nullable
+    const int* sub;     // nullable
+    int n, cap;
+    const int* prev_mid;   // nullable: no priors at all
+    const float* prev_xy;
+    const float* prev_ur;
+    const int* prev_n;     // nullable
+    int prev_n_host;
+    size_t prev_stride;
+    int prev_n_stride;
+    int prev_cap;
+    const int* prev_epoch;  // nullable
+    const int* cur_epoch;
+    int* d_prior;
+    int* n_out;  // nullable
+};
+hipError_t launch_row_priors(const RowPriorsBatch& b, int nseq, int max_n, hipStream_t st);
 
 // Batched residual scoring: blockIdx.z = sequence, blockIdx.y = hypothesis.
 // Sequence s: obj/img points [s*cap, s*cap + n_s), hypotheses [s*m, s*m + m),

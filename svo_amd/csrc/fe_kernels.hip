@@ -525,11 +525,16 @@ __global__ __launch_bounds__(kFeBlock) void stereo_prep_kernel(StereoPrepBatch B
 
 // The frame's feature list as the step leaves it into the sequence's ring slot,
 // stamped with the map epoch its ids belong to.
+// TRK (svo_frontend_set_stereo_tracking): a tracked feature's right column is its
+// own match in this frame (trk_next's x where trk_status is 1) instead of -1.
+template <bool TRK>
 __global__ __launch_bounds__(kFeBlock) void window_record_kernel(WindowRing R, int slot, const int* __restrict__ n_in,
                                                                  const float* __restrict__ xy_in,
                                                                  const int* __restrict__ mid_in,
                                                                  const float* __restrict__ ur_in,
-                                                                 const int* __restrict__ added) {
+                                                                 const int* __restrict__ added,
+                                                                 const float* __restrict__ trk_next,
+                                                                 const uint8_t* __restrict__ trk_status) {
     const int s = blockIdx.x;
     const int n = min(max(n_in[s], 0), R.cap);
     const size_t src = (size_t)s * R.cap, dst = ((size_t)s * R.window + slot) * R.cap;
@@ -541,7 +546,14 @@ __global__ __launch_bounds__(kFeBlock) void window_record_kernel(WindowRing R, i
     }
     if (R.ur) {  // the frame's own features are the last added[s] of its list
         const int n0 = max(n_in[s] - max(added[s], 0), 0);
-        for (int i = threadIdx.x; i < n; i += kFeBlock) R.ur[dst + i] = i < n0 ? -1.f : ur_in[src + i];
+        for (int i = threadIdx.x; i < n; i += kFeBlock) {
+            float v = -1.f;
+            if (i >= n0)
+                v = ur_in[src + i];
+            else if (TRK && trk_status[src + i])
+                v = trk_next[2 * (src + i)];
+            R.ur[dst + i] = v;
+        }
     }
     if (threadIdx.x == 0) {
         R.n[s * R.window + slot] = n;
@@ -575,9 +587,15 @@ __global__ __launch_bounds__(64) void window_select_kernel(WindowRing R, WindowO
 }  // namespace
 
 hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid,
-                                const float* ur, const int* added, int nseq, hipStream_t st) {
+                                const float* ur, const int* added, int nseq, hipStream_t st, const float* trk_next,
+                                const uint8_t* trk_status) {
     if (slot < 0 || slot >= r.window || (r.ur && (!ur || !added))) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(window_record_kernel, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid, ur, added);
+    if (trk_next && trk_status && r.ur)
+        hipLaunchKernelGGL(window_record_kernel<true>, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid, ur,
+                           added, trk_next, trk_status);
+    else
+        hipLaunchKernelGGL(window_record_kernel<false>, dim3(nseq), dim3(kFeBlock), 0, st, r, slot, n, xy, mid, ur,
+                           added, nullptr, nullptr);
     return hipGetLastError();
 }
 

@@ -184,12 +184,16 @@ struct WindowRing {
     int* map_epoch;  // [s]
     float* ur;       // [s][window][cap], the stereo window only (null otherwise): the right
                      // column of the match that created the feature in this frame, -1 if tracked
+                     // (svo_frontend_set_stereo_tracking: a tracked feature's own match in this frame)
 };
 // xyA / midA / nA as the step leaves them into `slot` of every sequence; with a
 // stereo ring also ur [s][cap] (AppendBatch::ur) for the last added[s] features of
-// each list, the frame's new ones, and -1 for the tracked ones in front of them
+// each list, the frame's new ones, and -1 for the tracked ones in front of them --
+// or, with trk_next / trk_status ([s][cap] pairs / flags, the guided match of this
+// frame's tracked features), trk_next's x where trk_status is 1
 hipError_t launch_window_record(const WindowRing& r, int slot, const int* n, const float* xy, const int* mid,
-                                const float* ur, const int* added, int nseq, hipStream_t st);
+                                const float* ur, const int* added, int nseq, hipStream_t st,
+                                const float* trk_next = nullptr, const uint8_t* trk_status = nullptr);
 // The recorded slots, oldest first (the same for every sequence: the ring turns
 // in lockstep); per sequence those of the current epoch are valid:
 // sel_slot / sel_cnt [s][window] (the valid slots first, zero counts behind), n_cams [s].

@@ -295,6 +295,59 @@ void fe_set_pose(svo_frontend* fe, int s, bool ok, const double rvec[3], const d
     for (int i = 0; i < 3; i++) T[9 + i] = -(T[3 * i] * tvec[0] + T[3 * i + 1] * tvec[1] + T[3 * i + 2] * tvec[2]);
 }
 
+// svo_frontend_set_stereo_tracking: the right columns of frame t's tracked features
+// -- the first nA - added of the list -- ahead of the record, on its stream: the
+// priors from the window's slot of frame t - 1 (the slot before `slot`, if it holds
+// that frame; the kernel compares its epoch with the map's), then the guided match
+// between level 0 of frame t's own images into trk_next / trk_status. The upload
+// stream waits for ev_trk before it streams another frame into t's image slot.
+static int fe_track_stereo(svo_frontend* fe, int t, int slot, hipStream_t st) {
+    svo_ctx* ctx = fe->ctx;
+    const FeWindow& w = fe->win;
+    const int S = fe->S, CAP = fe->CAP;
+    const int pslot = (slot + w.slots - 1) % w.slots;
+    const bool lookup = fe->trk_guide > 0 && w.count > 0 && w.frame[pslot] == t - 1;
+    RowPriorsBatch pb{};
+    pb.mid = fe->midA;
+    pb.counts = fe->nA;
+    pb.sub = fe->added;
+    pb.cap = CAP;
+    if (lookup) {
+        const size_t o = (size_t)pslot * CAP;
+        pb.prev_mid = w.ring.mid + o;
+        pb.prev_xy = w.ring.xy + 2 * o;
+        pb.prev_ur = w.ring.ur + o;
+        pb.prev_n = w.ring.n + pslot;
+        pb.prev_epoch = w.ring.epoch + pslot;
+        pb.cur_epoch = w.ring.map_epoch;
+        pb.prev_stride = (size_t)w.slots * CAP;
+        pb.prev_n_stride = w.slots;
+        pb.prev_cap = CAP;
+    }
+    pb.d_prior = fe->trk_prior;
+    pb.n_out = fe->trk_n;
+    SVO_HIP(ctx, launch_row_priors(pb, S, CAP, st));
+    SVO_HIP(ctx, hipStreamWaitEvent(st, fe->ev_pyr_r_b[t & 1], 0));  // the right level 0's border
+    const PyrDesc* dl = fe->d_desc + (size_t)(t % fe->T) * S;
+    const PyrDesc* dr = fe->d_desc_r + (size_t)(t % fe->T) * S;
+    StereoRowsBatch rb{dl, dr, fe->xyA, fe->trk_next, fe->trk_status, nullptr, nullptr, fe->trk_n, 0, CAP};
+    // the tracked counts are the device's; the last step's tracked counts bound them
+    int bound = 0;
+    for (int s = 0; s < S; s++) bound = std::max(bound, fe->h_nB[s]);
+    bound = std::min(std::max(bound, 1), CAP);
+    if (lookup) {
+        // few features lack a prior (a lost match one frame ago, a sequence whose map
+        // was reclaimed): an eighth of the waves loop over them
+        SVO_HIP(ctx, launch_stereo_rows_guided(rb, S, bound, fe->trk, fe->trk_prior, fe->trk_guide, (bound + 7) / 8, st));
+    } else {
+        SVO_HIP(ctx, launch_stereo_rows(rb, S, bound, fe->trk, st));
+    }
+    const int is = t % fe->T;
+    SVO_HIP(ctx, hipEventRecord(fe->ev_trk[is], st));
+    fe->trk_rec[is] = 1;
+    return SVO_OK;
+}
+
 // The window's slot of frame t: the feature list as the step leaves it (xyA /
 // midA / nA) copied on stream st, which runs behind the frame's keyframe and ahead
 // of whatever rewrites those lists; the slot's pose is the identity until the
@@ -303,7 +356,15 @@ int fe_window_record(svo_frontend* fe, int t, hipStream_t st) {
     FeWindow& w = fe->win;
     if (!w.slots) return SVO_OK;
     const int slot = w.count % w.slots;
-    SVO_HIP(fe->ctx, launch_window_record(w.ring, slot, fe->nA, fe->xyA, fe->midA, w.ur_feat, fe->added, fe->S, st));
+    if (fe->trk_on) {
+        int rc = fe_track_stereo(fe, t, slot, st);
+        if (rc) return rc;
+        SVO_HIP(fe->ctx, launch_window_record(w.ring, slot, fe->nA, fe->xyA, fe->midA, w.ur_feat, fe->added, fe->S, st,
+                                              fe->trk_next, fe->trk_status));
+    } else {
+        SVO_HIP(fe->ctx,
+                launch_window_record(w.ring, slot, fe->nA, fe->xyA, fe->midA, w.ur_feat, fe->added, fe->S, st));
+    }
     w.frame[slot] = t;
     w.count++;
     for (int s = 0; s < fe->S; s++) {

@@ -465,6 +465,9 @@ void svo_frontend_destroy(svo_frontend* fe) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : fe->up.ev_free)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : fe->ev_trk)
+        if (e) (void)hipEventDestroy(e);
+    if (fe->trk_mem) (void)hipFree(fe->trk_mem);
     if (fe->up.stage) (void)hipFree(fe->up.stage);
     if (fe->rect_stage) (void)hipFree(fe->rect_stage);
     orb_batch_destroy(fe->orb);
@@ -512,6 +515,40 @@ int svo_frontend_set_stereo_matcher(svo_frontend* fe, const svo_stereo_rows_para
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_matcher: parameters out of range");
     fe->rows = *params;
     fe->rows_on = true;
+    return SVO_OK;
+}
+
+int svo_frontend_set_stereo_tracking(svo_frontend* fe, const svo_stereo_rows_params* params, int guide) {
+    if (!fe || !params) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (!fe->win.ring.ur)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_tracking: no stereo window enabled");
+    if (fe->ahead.stepped >= 0 || fe->trk_on)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_tracking: once, after "
+                                           "svo_frontend_window_enable_stereo and before svo_frontend_init");
+    if (!stereo_rows_params_ok(*params) || guide < 0 || guide > 15)
+        return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_tracking: parameters out of range "
+                                           "(svo_stereo_match_rows', guide 0..15)");
+    const size_t n = (size_t)fe->S * fe->CAP;
+    size_t bytes = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1) SVO_HIP(ctx, hipMalloc(&fe->trk_mem, bytes));
+        char* p = pass == 0 ? nullptr : (char*)fe->trk_mem;
+        char* const p0 = p;
+        fe->trk_prior = carve<int>(p, n);
+        fe->trk_n = carve<int>(p, fe->S);
+        fe->trk_next = carve<float>(p, 2 * n);
+        fe->trk_status = carve<uint8_t>(p, n);
+        bytes = (size_t)(p - p0) + 256;
+    }
+    SVO_HIP(ctx, hipMemsetAsync(fe->trk_mem, 0, bytes, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fe->ev_trk.assign(fe->T, nullptr);
+    for (auto& e : fe->ev_trk) SVO_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    fe->trk_rec.assign(fe->T, 0);
+    fe->trk = *params;
+    fe->trk_guide = guide;
+    fe->trk_on = true;
     return SVO_OK;
 }
 
@@ -572,6 +609,10 @@ int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* lef
     // the slot waits for it on the device, not only by the host's window above
     if (up.free_rec[slot]) SVO_HIP(ctx, hipStreamWaitEvent(up.st, up.ev_free[slot], 0));
     up.free_rec[slot] = 0;
+    // ... and, with svo_frontend_set_stereo_tracking, by the guided match of that
+    // frame's tracked features behind its keyframe (fe_track_stereo)
+    if (fe->trk_on && fe->trk_rec[slot]) SVO_HIP(ctx, hipStreamWaitEvent(up.st, fe->ev_trk[slot], 0));
+    if (fe->trk_on) fe->trk_rec[slot] = 0;
     for (int side = 0; side < 2; side++) {
         const uint8_t* const* src = side ? right : left;
         uint8_t* dst = up.stage + (size_t)side * S * up.cap;

@@ -148,6 +148,19 @@ struct svo_frontend {
     // svo_frontend_set_stereo_matcher: row SAD (launch_stereo_rows) in place of the stereo LK
     bool rows_on = false;
     svo_stereo_rows_params rows{};
+    // svo_frontend_set_stereo_tracking: the guided row match of every recorded
+    // frame's tracked features (fe_window_record), its buffers ([s][CAP]; trk_n [s]:
+    // the tracked counts) and, per image ring slot, the event behind the match
+    // that read the slot's frame (a streamed upload into the slot waits for it)
+    bool trk_on = false;
+    svo_stereo_rows_params trk{};
+    int trk_guide = 0;
+    void* trk_mem = nullptr;
+    int *trk_prior = nullptr, *trk_n = nullptr;
+    float* trk_next = nullptr;
+    uint8_t* trk_status = nullptr;
+    std::vector<hipEvent_t> ev_trk;
+    std::vector<char> trk_rec;
     uint8_t* rect_stage = nullptr;  // set_frame with maps: the raw pair's staging ([2 side][rect_cap])
     size_t rect_cap = 0;
     // device state (one allocation, in carve order)
