@@ -121,7 +121,9 @@ typedef const __attribute__((address_space(1))) uint8_t* gu8;  // global (not fl
 typedef const __attribute__((address_space(1))) uint32_t* gu32;
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint16_t u16a1 __attribute__((aligned(1)));  // unaligned 2-byte global loads
+typedef uint32_t u32a1 __attribute__((aligned(1)));  // dword loads at any byte address (tools/unaligned_probe.hip)
 typedef const __attribute__((address_space(4))) PyrDesc* cpyr;  // scalar (s_load) descriptor reads
 
 // Global loads at a wave-uniform base plus an unsigned 32-bit byte offset: the

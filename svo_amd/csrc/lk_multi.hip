@@ -2,6 +2,7 @@
 // (temporal 21 x 21 with the min-eigenvalue error, stereo 11 x 11 without error).
 // The shape and staging of the groups' next-image regions are lk_quad.hpp's.
 #include "lk_quad.hpp"
+#include "lk_strip_map.hpp"
 #include "xcd_tile.hpp"
 
 namespace svo {
@@ -173,6 +174,19 @@ __global__ __launch_bounds__(64, MINW) void lk_multi_kernel(LKBatch B, LKDev p) 
     constexpr int NSTRIP = WW * (WH / NR);
     constexpr int LPF = 64 / FPW;                 // lanes per feature
     constexpr int K = (NSTRIP + LPF - 1) / LPF;   // strips per lane
+    using SM = StripMap<WW, WH / NR, LPF>;        // which strips (lk_strip_map.hpp)
+    static_assert(SM::K == K && SM::valid(), "strip map");
+    // triples: a lane's strips 0, 1, 2 from one dword (4 prev pixels) and one 16-byte
+    // load (4 derivative records) per row, its strip 3 loaded as a single strip
+    constexpr bool TRI = SM::TRIPLES;
+    static_assert(!TRI || K == 4, "a triple and a single per lane");
+    // A prev window starts at x in [-WW, w), y in [-WH, h) (window_in_bounds). A
+    // strip at column c reads pixels and records c, c + 1 of rows y .. y + WH; a
+    // triple's wide loads at column c <= WW - 3 read c .. c + 3, the columns its
+    // three strips read one by one -- under either map columns x .. x + WW and no
+    // further (SM::valid(): every strip a window column), inside the padded levels:
+    static_assert(WW + 1 <= kPyrPad && WH + 1 <= kPyrPad && WW + 1 <= kDerPad && WH + 1 <= kDerPad,
+                  "padding too small for the prev window's loads");
     // an odd strip height pairs the last rows of strips 2i and 2i + 1 (ODD; K even),
     // otherwise the last row is closed by a zero row
     constexpr bool ODD = NR % 2 == 1 && K % 2 == 0;
@@ -212,16 +226,15 @@ next_tile:  // (LOOP: the block's next tile, gridDim.x further on)
     const unsigned* jmine = jregs + g * (Q::JSTRIDE / 4);
     const StageGeom<JRW, JRH> sg(lane);
 
-    // the lane's strips: column, first row, LDS offset; slots past NSTRIP are dummies
+    // the lane's strips: column, first row; dummy slots carry zero weights
     int scol[K], srow[K];
     bool sreal[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        const int sidx = l + LPF * k;
-        sreal[k] = sidx < NSTRIP;
-        const int sc = sreal[k] ? sidx : 0;
-        scol[k] = sc % WW;
-        srow[k] = (sc / WW) * NR;
+        const Strip s = SM::at(l, k);
+        sreal[k] = s.real;
+        scol[k] = s.col;
+        srow[k] = s.band * NR;
     }
     constexpr float halfWx = (WW - 1) * 0.5f, halfWy = (WH - 1) * 0.5f;
     const int rnd_j = 1 << (W_BITS - 6 + kJShift);
@@ -297,6 +310,12 @@ next_tile:  // (LOOP: the block's next tile, gridDim.x further on)
             const gu8 ibase = pad_origin(I.data, I.pitch, kPyrPad, 1);
             const gu8 dbase = pad_origin((const uint8_t*)dprev.data[level], dpitch, kDerPad, 4);
             const int sx = inb ? ipx : 0, sy = inb ? ipy : 0;
+            const auto write_staging = [&] {
+#pragma unroll
+                for (int f = 0; f < FPW; f++)
+#pragma unroll
+                    for (int q = 0; q < SL::NPS; q++) sg.write(jregs + f * (Q::JSTRIDE / 4), sg.row(q), sv[f][q]);
+            };
             const auto load_strip = [&](int k, unsigned* P, u32x2a4* Dv) {
                 // per-lane offsets of the strip's first row; the rows by wave-uniform bases
                 const int x = sx + scol[k], y = sy + srow[k];
@@ -309,30 +328,59 @@ next_tile:  // (LOOP: the block's next tile, gridDim.x further on)
                     Dv[r] = ldg_off<u32x2a4>(dbase + (size_t)r * 4 * dpitch, od);
                 }
             };
-            const auto write_staging = [&] {
-#pragma unroll
-                for (int f = 0; f < FPW; f++)
-#pragma unroll
-                    for (int q = 0; q < SL::NPS; q++) sg.write(jregs + f * (Q::JSTRIDE / 4), sg.row(q), sv[f][q]);
+            const auto setup_strip = [&](int k, const unsigned* P, const u32x2a4* Dv) {
+                strip_setup_c<NR, ODD>(P, Dv, IW0, IW1, sreal[k] ? IW0 : 0u, sreal[k] ? IW1 : 0u, GX[k], GY[k], asum[0],
+                                       asum[1], asum[2], csum[0], csum[1], li[k], lx[k], ly[k]);
+                if (ODD && (k & 1))
+                    odd_pair_setup(li[k - 1], lx[k - 1], ly[k - 1], li[k], lx[k], ly[k], GXO[k / 2], GYO[k / 2],
+                                   asum[0], asum[1], asum[2], csum[0], csum[1]);
             };
-            // strips KKS at a time: loads of a group in flight together
-            static_assert(KKS >= 1, "strips loaded per setup group");
+            if constexpr (TRI) {
+                // the rows of strips 0, 1, 2 (columns c, c + 1, c + 2) in one dword -- pixels
+                // c .. c + 3, at any byte address -- and one 16-byte load -- records c .. c + 3
+                // -- each; the single strip 3's narrow loads go out once strips 0 and 1
+                // have freed their registers
+                unsigned M[NR + 1];
+                u32x4a4 Dm[NR + 1];
+                {
+                    const int x = sx + scol[0], y = sy + srow[0];
+                    const unsigned oi = (unsigned)(x + kPyrPad) + (unsigned)(y + kPyrPad) * (unsigned)I.pitch;
+                    const unsigned od = 4u * ((unsigned)(x + kDerPad) + (unsigned)(y + kDerPad) * (unsigned)dpitch);
 #pragma unroll
-            for (int k0 = 0; k0 < K; k0 += KKS) {
-                constexpr int KK = K >= KKS ? KKS : 1;
-                unsigned P[KK][NR + 1];
-                u32x2a4 Dv[KK][NR + 1];
+                    for (int r = 0; r <= NR; r++) {
+                        M[r] = ldg_off<u32a1>(ibase + (size_t)r * I.pitch, oi);
+                        Dm[r] = ldg_off<u32x4a4>(dbase + (size_t)r * 4 * dpitch, od);
+                    }
+                }
+                write_staging();
+                unsigned P[NR + 1], Ps[NR + 1];
+                u32x2a4 Dv[NR + 1], Ds[NR + 1];
 #pragma unroll
-                for (int kk = 0; kk < KK; kk++) load_strip(k0 + kk, P[kk], Dv[kk]);
-                if (k0 == 0) write_staging();
+                for (int k = 0; k < 3; k++) {
+                    if (k == 2) load_strip(3, Ps, Ds);
 #pragma unroll
-                for (int kk = 0; kk < KK; kk++) {
-                    const int k = k0 + kk;
-                    strip_setup_c<NR, ODD>(P[kk], Dv[kk], IW0, IW1, sreal[k] ? IW0 : 0u, sreal[k] ? IW1 : 0u, GX[k],
-                                           GY[k], asum[0], asum[1], asum[2], csum[0], csum[1], li[k], lx[k], ly[k]);
-                    if (ODD && (k & 1))
-                        odd_pair_setup(li[k - 1], lx[k - 1], ly[k - 1], li[k], lx[k], ly[k], GXO[k / 2], GYO[k / 2],
-                                       asum[0], asum[1], asum[2], csum[0], csum[1]);
+                    for (int r = 0; r <= NR; r++) {
+                        P[r] = __builtin_amdgcn_perm(0u, M[r], k == 0 ? 0x0c010c00u : k == 1 ? 0x0c020c01u : 0x0c030c02u);
+                        Dv[r] = k == 0   ? u32x2a4{Dm[r].x, Dm[r].y}
+                                : k == 1 ? u32x2a4{Dm[r].y, Dm[r].z}
+                                         : u32x2a4{Dm[r].z, Dm[r].w};
+                    }
+                    setup_strip(k, P, Dv);
+                }
+                setup_strip(3, Ps, Ds);
+            } else {
+                // strips KKS at a time: loads of a group in flight together
+                static_assert(KKS >= 1, "strips loaded per setup group");
+#pragma unroll
+                for (int k0 = 0; k0 < K; k0 += KKS) {
+                    constexpr int KK = K >= KKS ? KKS : 1;
+                    unsigned P[KK][NR + 1];
+                    u32x2a4 Dv[KK][NR + 1];
+#pragma unroll
+                    for (int kk = 0; kk < KK; kk++) load_strip(k0 + kk, P[kk], Dv[kk]);
+                    if (k0 == 0) write_staging();
+#pragma unroll
+                    for (int kk = 0; kk < KK; kk++) setup_strip(k0 + kk, P[kk], Dv[kk]);
                 }
             }
         }
@@ -502,9 +550,8 @@ next_tile:  // (LOOP: the block's next tile, gridDim.x further on)
                 const unsigned TXO = gb.z, TYO = gb.w;
                 int soff;
                 {
-                    const int sidx = ((lane >> 1) & (LPF - 1)) + LPF * (((lane >> 5) << 1) | (lane & 1));
-                    const int sc = sidx < NSTRIP ? sidx : 0;
-                    soff = (sc / WW) * NR * JRW + sc % WW;
+                    const Strip s = SM::at((lane >> 1) & (LPF - 1), ((lane >> 5) << 1) | (lane & 1));
+                    soff = s.band * NR * JRW + s.col;
                 }
                 float tnx = rl_f(nextx, ls), tny = rl_f(nexty, ls), tpdx = rl_f(pdx, ls), tpdy = rl_f(pdy, ls);
                 float tox = rl_f(nx, ls), toy = rl_f(ny, ls);
@@ -617,7 +664,13 @@ hipError_t launch_multi(const LKBatch& b, int nseq, int max_n, const LKParams& l
 // and than 3 px; two features per wave (lk_dual_kernel, another lane
 // map) measured slower and is gone; 4 waves/SIMD, 8 features per wave
 // and one strip ahead in the setup measured slower: DESIGN.md section 5).
-// Launch bound 3 waves per SIMD, strips loaded two at a time in the setup.
+// Launch bound 3 waves per SIMD (the kernel compiles to 122 VGPRs and runs 4).
+// The level setup was bound by the texture addresser, which a load costs the same
+// at any width and with any lanes active: a lane's strips 0, 1, 2 are three neighbouring columns read by one
+// dword and one 16-byte load per row, strip 3 a single column (lk_strip_map.hpp;
+// KKS, the strips per load group of the dealt map, is unused by it) -- 32 strip
+// loads per level and wave where the dealt map issued 64
+// (profiles/lk_pair_loads.txt).
 hipError_t launch_lk_multi_temporal(const LKBatch& b, int nseq, int max_n, const LKParams& lp, hipStream_t st) {
     return launch_multi<4, 1, 3, 2, 21, 21, 7, false>(b, nseq, max_n, lp, st);
 }

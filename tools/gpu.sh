@@ -15,6 +15,7 @@
 #   lksplit                 LK VALU / time with the iteration cap at 1, 2, 50
 #   lkab "V1 V2 .."         standalone LK kernel time per SVO_LK_VARIANT (or $LKAB_VAR) value
 #   lkmem [LIB ..]          LK memory-pipeline + issue counters (TA, TCP, SQ), per library build
+#   taprobe                 tools/ta_load_probe: time and TA_TA_BUSY per load width and active lanes
 #   ab VAR "V1 V2" [RUNS]   bench A/B of an environment switch
 #   abcfg VAR "V1 V2"       the same A/B at the 1080p, 4K and KITTI configs
 #   round1 TAG / round2 TAG  the round records: tests, smoke, driver bench + rocprof / PMC, mix, 1080p + 4K
@@ -197,6 +198,30 @@ P
     done
 }
 
+run_taprobe() {
+    local P=tools/bin/ta_load_probe
+    [ -x $P ] || fail "build $P first (the command is at the top of tools/ta_load_probe.hip)"
+    timeout -k 10 120 $P > $O/ta_probe.txt 2>&1 || fail taprobe $O/ta_probe.txt
+    rm -rf /tmp/tap
+    timeout -s KILL 120 rocprofv3 --pmc TA_TA_BUSY_sum TA_BUSY_avr GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD SQ_WAVES -d /tmp/tap -o run \
+        --output-format csv -- $P > $O/ta_probe_pmc.log 2>&1 || fail taprobe-pmc $O/ta_probe_pmc.log
+    python3 - >> $O/ta_probe.txt <<'P'
+import csv, glob, collections, re
+agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(set)
+for f in glob.glob('/tmp/tap/**/*counter_collection.csv', recursive=True):
+    for r in csv.DictReader(open(f)):
+        m = re.search(r'ta_probe_kernel<([^>]*)>', r['Kernel_Name'])
+        if not m: continue
+        agg[m.group(1)][r['Counter_Name']] += float(r['Counter_Value']); n[m.group(1)].add(r['Dispatch_Id'])
+print("counters per dispatch (rocprofv3 --pmc, a pass of its own):")
+for k, d in agg.items():
+    c = len(n[k]); v = d.get('SQ_INSTS_VMEM_RD', 0) / c
+    print(f"  <{k:42s}> " + ' '.join(f"{a}={b / c:.0f}" for a, b in sorted(d.items()))
+          + (f" TA_BUSY_sum/VMEM={d.get('TA_TA_BUSY_sum', 0) / c / v:.2f}" if v else ""))
+P
+    cat $O/ta_probe.txt
+}
+
 run_ab() {
     local var=$1 vals=$2 runs=${3:-2}
     for r in $(seq $runs); do for v in $vals; do
@@ -261,6 +286,7 @@ while [ $# -gt 0 ]; do
         lksplit) run_lksplit ;;
         lkab) run_lkab "${args[@]}" ;;
         lkmem) run_lkmem "${args[@]}" ;;
+        taprobe) run_taprobe ;;
         ab) run_ab "${args[@]}" ;;
         abcfg) run_abcfg "${args[@]}" ;;
         round1) run_round1 "${args[@]}" ;;
