@@ -363,6 +363,61 @@ int svo_reprojection_jacobians(svo_ctx* ctx, const double* obj_xyz, const float*
 int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, const int* counts, int n_problems,
                      int max_n, const double K[9], double huber_delta, int max_iterations, double* poses,
                      double* costs, int* iterations);
+/* Motion-only refinement from stereo observations, on the device (§8 a11d): the
+ * pose of each problem from its observations with the points held constant
+ * (ORB-SLAM's motion-only BA), svo_refine_poses' Levenberg-Marquardt rule by
+ * rule -- lambda from 1e-4; A_ii += lambda (A_ii > 0 ? A_ii : 1e-12); Cholesky,
+ * lambda x10 up to 1e16 while not positive definite, then the problem ends; the
+ * step rule |dx| < 1e-12 (1 + |t|); T <- exp(xi^) T; accept if c1 <= c0, then
+ * lambda <- max(0.1 lambda, 1e-12) and stop if c0 - c1 <= 1e-15 c0; else lambda
+ * x10, stop at 1e16 -- kept per problem and run, all of it, by one workgroup in
+ * one launch: one upload, one launch, one download, whatever max_iterations is.
+ * Inputs as svo_reprojection_jacobians' plus img_ur (P*max_n floats): the right
+ * image's column of each observation, < 0 for a monocular one, and the rig's
+ * baseline. Every observation is evaluated as svo_bundle_adjust_stereo states it
+ * below (the third residual and its pose-Jacobian row, the Huber norm over the
+ * residual the observation has, Pz <= 0 contributes nothing, ur < 0 exactly
+ * svo_reprojection_jacobians' evaluation); the points do not move. All
+ * arithmetic is double. The 28 sums (H 21, g 6, cost) of a problem of n
+ * observations are formed in one order: thread t of 256 adds observations t,
+ * t + 256, ... in ascending order (starting from the first one's terms; an
+ * observation that contributes nothing adds +0); the 64 lanes of each wave are
+ * summed by the xor butterfly 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) +
+ * w2) + w3. For n <= 256 and img_ur all negative that is
+ * svo_reprojection_jacobians' normal, bit for bit. The order depends on nothing
+ * outside the problem (not on n_problems, max_n or the other problems), so a
+ * problem gets the same bits alone and in any batch, run after run.
+ * poses: in/out. costs: P x 2 (initial, final). iterations: P, the iterations
+ * each problem began, the one that gives up or stops on the step rule included
+ * (svo_bundle_adjust's convention). normal: P x 28 = H, g, cost at the returned
+ * pose; H is the undamped sum w J^T J, the pose's information matrix (its
+ * inverse is the covariance of xi for unit pixel noise). All three may be NULL.
+ * max_iterations == 0 is a pure linearisation: poses keep their bits, both costs
+ * are equal, iterations are 0. Values that are not finite follow
+ * svo_bundle_adjust's rule: a problem with a NaN or an infinity in its pose, or
+ * within its count in its points, img_xy or img_ur, or whose initial cost is not
+ * finite, is not iterated on; its pose keeps its bits, its costs and its normal
+ * are NaN, its iteration count is 0, and the other problems get what they get
+ * alone. n_problems == 0 or max_n == 0: SVO_OK (max_n == 0: every problem is the
+ * empty one, cost 0, pose bits kept). SVO_ERR_ARG (nothing written):
+ * svo_refine_poses' bad arguments; img_ur NULL with work to do; baseline not
+ * finite or <= 0; max_iterations outside 0 .. SVO_REFINE_MAX_ITERATIONS (the
+ * bound that keeps a launch finite on any input). */
+#define SVO_REFINE_MAX_ITERATIONS 1000
+int svo_refine_poses_stereo(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, const float* img_ur,
+                            const int* counts, int n_problems, int max_n, const double K[9], double baseline,
+                            double huber_delta, int max_iterations, double* poses, double* costs, int* iterations,
+                            double* normal);
+/* svo_refine_poses_stereo's launch timed with HIP events: reps launches after one
+ * warm-up, each from `poses` (which stay as they are), ms per whole LM launch
+ * (ms_device). Beside it the wall time per call of svo_refine_poses (ms_host: the
+ * host loop, one round trip per iteration) on the same img_xy from the same
+ * poses with the same max_iterations, reps calls after one warm-up; it ignores
+ * img_ur. SVO_ERR_ARG in addition: nothing to run, reps <= 0, an output NULL. */
+int svo_refine_poses_time(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, const float* img_ur,
+                          const int* counts, int n_problems, int max_n, const double K[9], double baseline,
+                          double huber_delta, int max_iterations, const double* poses, int reps, double* ms_device,
+                          double* ms_host);
 
 /* ------------------------------------------------------------ windowed bundle adjustment
  * Poses and points together: the back end the reference promises (Map::run's
@@ -729,6 +784,24 @@ int svo_frontend_window_right(svo_frontend* fe, int seq, int cap, float* ur);
  * svo_frontend_window_right. SVO_ERR_ARG in addition: no stereo window enabled. */
 int svo_frontend_bundle_adjust_stereo(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations,
                                       double* costs, int* iterations, int* sizes);
+/* svo_refine_poses_stereo for the newest frame of every sequence, from the window
+ * on the device (opt-in; needs svo_frontend_window_enable or _enable_stereo). Like
+ * svo_frontend_bundle_adjust it calls svo_frontend_synchronize first and uses the
+ * slots of the map's current epoch. Per sequence the problem is the newest valid
+ * slot: its pixels, its right columns (a plain window: every observation
+ * monocular), its pose, the map points its ids name (read in place, no gather
+ * pass) and baseline = -P_right[3] / P_right[0]. The refined pose is written into
+ * that slot's pose, where svo_frontend_bundle_adjust writes poses, and nowhere
+ * else: the map, svo_frontend_pose and every later svo_frontend_step are unchanged
+ * to the bit. The results equal svo_refine_poses_stereo's, bit for bit, on the
+ * same arrays read back beforehand. A sequence without a valid slot is the empty
+ * problem (cost 0, one iteration, nothing written). costs: S x 2, iterations: S,
+ * counts: S (the observations used); any may be NULL; one download brings the
+ * three. SVO_ERR_ARG: no window enabled; max_iterations outside 0 ..
+ * SVO_REFINE_MAX_ITERATIONS; a plain window whose P_right gives no baseline > 0
+ * still runs (no observation uses it). */
+int svo_frontend_refine_poses(svo_frontend* fe, double huber_delta, int max_iterations, double* costs,
+                              int* iterations, int* counts);
 /* Stereo columns for tracked features (opt-in; RECTIFIED frames): from this call
  * on every recorded frame also matches its tracked features -- the first
  * nA - added of the list the step leaves -- between level 0 of its own left and

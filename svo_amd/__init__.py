@@ -144,6 +144,10 @@ _SIGS = [
                                              C.c_double, _f64p, _f64p, _f64p]),
     ("svo_refine_poses", C.c_int, [_vp, _f64p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_double, C.c_int,
                                    _f64p, _f64p, _i32p]),
+    ("svo_refine_poses_stereo", C.c_int, [_vp, _f64p, _f32p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_double,
+                                          C.c_double, C.c_int, _f64p, _f64p, _i32p, _f64p]),
+    ("svo_refine_poses_time", C.c_int, [_vp, _f64p, _f32p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_double,
+                                        C.c_double, C.c_int, _f64p, C.c_int, _f64p, _f64p]),
     ("svo_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
                                     _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_int, _f64p, _i32p]),
     ("svo_ba_linearize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
@@ -177,6 +181,7 @@ _SIGS = [
     ("svo_frontend_window_enable_stereo", C.c_int, [_vp, C.c_int]),
     ("svo_frontend_window_right", C.c_int, [_vp, C.c_int, C.c_int, _f32p]),
     ("svo_frontend_bundle_adjust_stereo", C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
+    ("svo_frontend_refine_poses", C.c_int, [_vp, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
     ("svo_frontend_time_pyramid", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_time_fast", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_pyramid_level", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
@@ -768,6 +773,50 @@ class Context:
                                            _p(costs, _f64p), C.byref(it)))
         return poses, costs, it.value
 
+    @staticmethod
+    def _refine_stereo_args(obj, img_pts, ur, poses, K, counts):
+        obj = _c(obj, np.float64)
+        if obj.ndim == 2:
+            obj = obj[None]
+        P, n = obj.shape[0], obj.shape[1]
+        img_pts = _c(img_pts, np.float32).reshape(P, n, 2)
+        ur = _c(ur, np.float32).reshape(P, n) if ur is not None else None
+        poses = np.array(poses, np.float64).reshape(P, 12)
+        K = _c(K, np.float64).reshape(9)
+        cnt = _c(counts, np.int32).reshape(P) if counts is not None else None
+        return P, n, obj, img_pts, ur, poses, K, cnt
+
+    def refine_poses_stereo(self, obj, img_pts, ur, poses, K, baseline, counts=None, huber_delta: float = 0.0,
+                            max_iterations: int = 20):
+        """Motion-only LM over SE(3) from stereo observations, the whole run of every
+        problem in one launch (svo_refine_poses_stereo): obj (P, n, 3) f64, img_pts
+        (P, n, 2) f32, ur (P, n) f32 right columns (< 0: a monocular observation),
+        poses (P, 12) -> (poses (P, 12), costs (P, 2): initial and final, iterations
+        (P,), normal (P, 28): H, g, cost at the returned pose; H is the pose's
+        information matrix). max_iterations = 0: the linearisation alone."""
+        P, n, obj, img_pts, ur, poses, K, cnt = self._refine_stereo_args(obj, img_pts, ur, poses, K, counts)
+        costs = np.zeros((P, 2), np.float64)
+        its = np.zeros(P, np.int32)
+        ne = np.zeros((P, 28), np.float64)
+        self._check(lib().svo_refine_poses_stereo(
+            self.handle, _p(obj, _f64p), _p(img_pts, _f32p), _p(ur, _f32p) if ur is not None else None,
+            _p(cnt, _i32p) if cnt is not None else None, P, n, _p(K, _f64p), float(baseline), float(huber_delta),
+            int(max_iterations), _p(poses, _f64p), _p(costs, _f64p), _p(its, _i32p), _p(ne, _f64p)))
+        return poses, costs, its, ne
+
+    def refine_poses_time(self, obj, img_pts, ur, poses, K, baseline, counts=None, huber_delta: float = 0.0,
+                          max_iterations: int = 10, reps: int = 10) -> dict:
+        """ms per whole LM launch of refine_poses_stereo (HIP events) and, wall time,
+        per call of refine_poses on the same pixels from the same poses with the same
+        iterations cap (svo_refine_poses_time)."""
+        P, n, obj, img_pts, ur, poses, K, cnt = self._refine_stereo_args(obj, img_pts, ur, poses, K, counts)
+        ms = np.zeros(2)
+        self._check(lib().svo_refine_poses_time(
+            self.handle, _p(obj, _f64p), _p(img_pts, _f32p), _p(ur, _f32p) if ur is not None else None,
+            _p(cnt, _i32p) if cnt is not None else None, P, n, _p(K, _f64p), float(baseline), float(huber_delta),
+            int(max_iterations), _p(poses, _f64p), int(reps), _p(ms[0:], _f64p), _p(ms[1:], _f64p)))
+        return {"ms_device": float(ms[0]), "ms_host": float(ms[1])}
+
     # ---------------------------------------------------------------- bundle adjustment
     @staticmethod
     def _ba_args(poses, fixed, points, obs_cam, obs_point, obs_xy, K, n_cams, n_points, n_obs):
@@ -1180,6 +1229,20 @@ class Frontend:
         self.ctx._check(adjust(self.handle, int(n_fixed), float(huber_delta), int(max_iterations), _p(costs, _f64p),
                                _p(its, _i32p), _p(sizes, _i32p)))
         return costs, its, sizes
+
+    def refine_poses(self, huber_delta=0.0, max_iterations=10):
+        """Motion-only refinement of every sequence's newest window frame from its
+        stereo observations, on the device (svo_frontend_refine_poses): the refined
+        pose goes into the window's newest slot and nowhere else -> (costs (S, 2):
+        initial and final, iterations (S,), counts (S,): observations used). A plain
+        window gives the monocular run."""
+        S = self.cfg.n_seq
+        costs = np.zeros((S, 2), np.float64)
+        its = np.zeros(S, np.int32)
+        cnt = np.zeros(S, np.int32)
+        self.ctx._check(lib().svo_frontend_refine_poses(self.handle, float(huber_delta), int(max_iterations),
+                                                        _p(costs, _f64p), _p(its, _i32p), _p(cnt, _i32p)))
+        return costs, its, cnt
 
     def time_pyramid(self, t, reps=20):
         """ms per pyramid + Scharr launch chain of frame t, timed alone."""

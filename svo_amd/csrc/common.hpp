@@ -80,7 +80,7 @@ struct svo_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     int64_t lk_iters = 0;
-    svo_scratch s[14];
+    svo_scratch s[15];
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // colour ingest: pinned double buffer (host copy of frame k+1 overlaps the

@@ -7,6 +7,7 @@
 
 #include "ba.hpp"
 #include "frontend_state.hpp"
+#include "pose_refine.hpp"
 
 namespace svo {
 
@@ -318,6 +319,56 @@ int svo_frontend_bundle_adjust(svo_frontend* fe, int n_fixed, double huber_delta
 int svo_frontend_bundle_adjust_stereo(svo_frontend* fe, int n_fixed, double huber_delta, int max_iterations,
                                       double* costs, int* iterations, int* sizes) {
     return fe_bundle_adjust(fe, true, n_fixed, huber_delta, max_iterations, costs, iterations, sizes);
+}
+
+int svo_frontend_refine_poses(svo_frontend* fe, double huber_delta, int max_iterations, double* costs,
+                              int* iterations, int* counts) {
+    if (!fe) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    const FeWindow& w = fe->win;
+    if (!w.slots) return set_error(ctx, SVO_ERR_ARG, "svo_frontend_refine_poses: no window enabled");
+    if (max_iterations < 0 || max_iterations > SVO_REFINE_MAX_ITERATIONS)
+        return set_error(ctx, SVO_ERR_ARG,
+                         "svo_frontend_refine_poses: max_iterations outside 0 .. SVO_REFINE_MAX_ITERATIONS");
+    // the newest frame's pose lands and its keyframe's points reach the world frame
+    int rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, launch_window_select(w.ring, fe_window_order(fe), fe->S, w.sel_slot, w.sel_cnt, w.sel_nc, st));
+    // the results: [S][2] costs, [S] iterations, [S] counts, one block and one download
+    const size_t S = (size_t)fe->S, bytes = S * (2 * sizeof(double) + 2 * sizeof(int));
+    char* d = (char*)scratch(ctx, 14, bytes);
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    PoseRefineBatch b;
+    b.P = fe->S;
+    b.cap = fe->CAP;
+    b.poses_in = b.poses_out = w.h_pose;
+    b.sel_slot = w.sel_slot;
+    b.sel_cnt = w.sel_cnt;
+    b.sel_nc = w.sel_nc;
+    b.window = w.slots;
+    b.map = fe->map;
+    b.map_cap = fe->MAPCAP;
+    b.ids = w.ring.mid;
+    b.xy = w.ring.xy;
+    b.ur = w.ring.ur;  // (null with the plain window: every observation monocular)
+    const double* K = fe->cfg.K;
+    b.fx = K[0], b.fy = K[4], b.cx = K[2], b.cy = K[5];
+    b.baseline = w.ring.ur ? fe_baseline(fe) : 1.0;
+    b.delta = huber_delta;
+    b.max_iterations = max_iterations;
+    b.costs = (double*)d;
+    b.iterations = (int*)(d + 2 * sizeof(double) * S);
+    b.n_used = b.iterations + S;
+    SVO_HIP(ctx, launch_pose_refine(b, st));
+    std::vector<char> h(bytes);
+    SVO_HIP(ctx, hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    const char* its = h.data() + 2 * sizeof(double) * S;
+    if (costs) std::memcpy(costs, h.data(), 2 * sizeof(double) * S);
+    if (iterations) std::memcpy(iterations, its, sizeof(int) * S);
+    if (counts) std::memcpy(counts, its + sizeof(int) * S, sizeof(int) * S);
+    return SVO_OK;
 }
 
 int svo_frontend_scharr_level(svo_frontend* fe, int seq, int t, int level, int16_t* ix, int16_t* iy, int stride) {

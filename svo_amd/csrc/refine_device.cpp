@@ -1,0 +1,166 @@
+// Motion-only stereo refinement, the C ABI around pose_refine.hip (§8 a11d):
+// svo_refine_poses_stereo (one upload, one launch, one download) and its timing
+// probe. The front end's entry, svo_frontend_refine_poses, is in frontend_api.cpp.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <vector>
+
+#include "pose_refine.hpp"
+
+using namespace svo;
+
+namespace {
+
+constexpr int kNE = kPoseRefineNE;
+
+struct Staged {
+    double *obj, *poses, *poses_out, *costs, *normal;
+    float *xy, *ur;
+    int *counts, *its;
+};
+
+const char* bad_args(const double* obj, const float* xy, const float* ur, const int* counts, int P, int max_n,
+                     const double* K, double baseline, int max_iterations, const double* poses) {
+    if (P < 0 || max_n < 0 || !K) return "sizes < 0 or K null";
+    if (P > 0 && !poses) return "poses null";
+    if (P > 0 && max_n > 0 && (!obj || !xy)) return "obj_xyz / img_xy null";
+    if (P > 0 && max_n > 0 && !ur) return "img_ur null";
+    if (!(std::isfinite(baseline) && baseline > 0)) return "baseline not finite or <= 0";
+    if (max_iterations < 0 || max_iterations > SVO_REFINE_MAX_ITERATIONS)
+        return "max_iterations outside 0 .. SVO_REFINE_MAX_ITERATIONS";
+    if (counts)
+        for (int b = 0; b < P; b++)
+            if (counts[b] < 0 || counts[b] > max_n) return "a count outside 0 .. max_n";
+    return nullptr;
+}
+
+// the inputs on the device (context stream) and the launch's arguments
+int stage(svo_ctx* ctx, const double* obj, const float* xy, const float* ur, const int* counts, int P, int max_n,
+          const double K[9], double baseline, double huber_delta, int max_iterations, const double* poses,
+          bool separate_out, Staged& s, PoseRefineBatch& b) {
+    const size_t np = (size_t)P * max_n;
+    const size_t bytes = sizeof(double) * (3 * np + (12 + 12 + 2 + kNE) * (size_t)P) + sizeof(float) * 3 * np +
+                         sizeof(int) * 2 * (size_t)P + 9 * 256;
+    char* d = (char*)scratch(ctx, 14, bytes);
+    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    auto carve = [&](size_t n) {
+        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
+        char* r = d;
+        d += n;
+        return r;
+    };
+    s.obj = (double*)carve(sizeof(double) * 3 * np);
+    s.poses = (double*)carve(sizeof(double) * 12 * P);
+    s.poses_out = separate_out ? (double*)carve(sizeof(double) * 12 * P) : s.poses;
+    s.costs = (double*)carve(sizeof(double) * 2 * P);
+    s.normal = (double*)carve(sizeof(double) * kNE * P);
+    s.xy = (float*)carve(sizeof(float) * 2 * np);
+    s.ur = (float*)carve(sizeof(float) * np);
+    s.counts = counts ? (int*)carve(sizeof(int) * P) : nullptr;
+    s.its = (int*)carve(sizeof(int) * P);
+    hipStream_t st = ctx->stream;
+    if (np) {
+        SVO_HIP(ctx, hipMemcpyAsync(s.obj, obj, sizeof(double) * 3 * np, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, hipMemcpyAsync(s.xy, xy, sizeof(float) * 2 * np, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, hipMemcpyAsync(s.ur, ur, sizeof(float) * np, hipMemcpyHostToDevice, st));
+    }
+    if (counts) SVO_HIP(ctx, hipMemcpyAsync(s.counts, counts, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(s.poses, poses, sizeof(double) * 12 * P, hipMemcpyHostToDevice, st));
+    b = PoseRefineBatch{};
+    b.P = P;
+    b.cap = max_n;
+    b.poses_in = s.poses;
+    b.poses_out = s.poses_out;
+    b.counts = s.counts;
+    b.obj = s.obj;
+    b.xy = s.xy;
+    b.ur = s.ur;
+    b.fx = K[0], b.fy = K[4], b.cx = K[2], b.cy = K[5];
+    b.baseline = baseline;
+    b.delta = huber_delta;
+    b.max_iterations = max_iterations;
+    b.costs = s.costs;
+    b.iterations = s.its;
+    b.normal = s.normal;
+    return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svo_refine_poses_stereo(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, const float* img_ur,
+                            const int* counts, int n_problems, int max_n, const double K[9], double baseline,
+                            double huber_delta, int max_iterations, double* poses, double* costs, int* iterations,
+                            double* normal) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (const char* why = bad_args(obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, max_iterations,
+                                   poses))
+        return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_stereo: %s", why);
+    if (n_problems == 0) return SVO_OK;
+    const size_t P = (size_t)n_problems;
+    Staged s;
+    PoseRefineBatch b;
+    int rc = stage(ctx, obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, huber_delta, max_iterations,
+                   poses, false, s, b);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, launch_pose_refine(b, st));
+    // one block: poses_out (= poses), costs and normal are carved side by side,
+    // each downloaded where the caller wants it
+    SVO_HIP(ctx, hipMemcpyAsync(poses, s.poses_out, sizeof(double) * 12 * P, hipMemcpyDeviceToHost, st));
+    if (costs) SVO_HIP(ctx, hipMemcpyAsync(costs, s.costs, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, st));
+    if (iterations) SVO_HIP(ctx, hipMemcpyAsync(iterations, s.its, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    if (normal) SVO_HIP(ctx, hipMemcpyAsync(normal, s.normal, sizeof(double) * kNE * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+int svo_refine_poses_time(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, const float* img_ur,
+                          const int* counts, int n_problems, int max_n, const double K[9], double baseline,
+                          double huber_delta, int max_iterations, const double* poses, int reps, double* ms_device,
+                          double* ms_host) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (const char* why = bad_args(obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, max_iterations,
+                                   poses))
+        return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_time: %s", why);
+    if (n_problems <= 0 || max_n <= 0 || reps <= 0 || !ms_device || !ms_host)
+        return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_time: bad arguments");
+    Staged s;
+    PoseRefineBatch b;
+    // every launch starts from the staged poses: the results go to a block of their own
+    int rc = stage(ctx, obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, huber_delta, max_iterations,
+                   poses, true, s, b);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    hipEvent_t e0, e1;
+    SVO_HIP(ctx, hipEventCreate(&e0));
+    SVO_HIP(ctx, hipEventCreate(&e1));
+    hipError_t e = launch_pose_refine(b, st);  // untimed first
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    for (int i = 0; i < reps && e == hipSuccess; i++) e = launch_pose_refine(b, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    SVO_HIP(ctx, e);
+    *ms_device = ms / reps;
+    // the host loop on the same left pixels from the same poses, the same iterations cap
+    std::vector<double> T((size_t)12 * n_problems);
+    double wall = 0;
+    for (int i = 0; i <= reps; i++) {  // (the first run is the warm-up)
+        std::copy(poses, poses + T.size(), T.begin());
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = svo_refine_poses(ctx, obj_xyz, img_xy, counts, n_problems, max_n, K, huber_delta, max_iterations,
+                              T.data(), nullptr, nullptr);
+        if (rc) return rc;
+        if (i) wall += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    *ms_host = wall / reps;
+    return SVO_OK;
+}
+
+}  // extern "C"
