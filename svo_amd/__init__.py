@@ -528,8 +528,10 @@ class Context:
 
     # ---------------------------------------------------------------- FAST
     def fast_detect(self, img: Image, threshold: int = 20, nonmax: bool = True, mask=None,
-                    cap: int = 1 << 20) -> np.ndarray:
-        """cv::FastFeatureDetector::detect -> float32 array (n, 3): x, y, response."""
+                    cap: int = 1 << 20, return_count: bool = False):
+        """cv::FastFeatureDetector::detect -> float32 array (n, 3): x, y, response; the
+        first `cap` keypoints when there are more. return_count: (that array,
+        svo_fast_detect's n_out: the number found, also when it exceeds cap)."""
         out = np.empty((cap, 3), np.float32)
         n = C.c_int()
         mp = None
@@ -539,7 +541,8 @@ class Context:
             mp = _p(mask, _u8p)
         self._check(lib().svo_fast_detect(self.handle, img.handle, int(threshold), int(bool(nonmax)), mp,
                                           _p(out, _f32p), cap, C.byref(n)))
-        return out[: min(n.value, cap)].copy()
+        kp = out[: min(n.value, cap)].copy()
+        return (kp, n.value) if return_count else kp
 
     def orb_detect(self, img: Image, params: "OrbParams" = None, mask=None, cap: int = 1 << 16):
         """cv::ORB::detect -> (float32 (n, 3) x, y, response; int32 (n,) octave)."""

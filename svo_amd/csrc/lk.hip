@@ -40,9 +40,12 @@ void lk_apply_env(LKParams& p) {
 
 bool lk_supported(int win_w, int win_h) {
     if (win_w < 3 || win_h < 3 || win_w + 2 * JM > 64 || win_w + 3 > 64) return false;
+    // a lane's strip: up to 64 rows (windows wider than 32 px have one strip per
+    // column), its int32 partial sums bounded by 64 * 8160 * 4080 < 2^31; at most
+    // 2048 px, the bound of the float SAD sum (2048 * 8160 < 2^24)
     int groups = 64 / win_w;
     int rpg = (win_h + groups - 1) / groups;
-    return rpg <= 32 && win_w * win_h <= 2048;
+    return rpg <= 64 && win_w * win_h <= 2048;
 }
 
 hipError_t launch_lk(const LKBatch& b, int nseq, int max_n, const LKParams& lp, hipStream_t st) {

@@ -40,6 +40,7 @@ constexpr int kExact24 = 1 << 24;
 
 template <int RPG, bool FULL>
 __global__ __launch_bounds__(64) void lk_cv_kernel(LKBatch B, LKDev p, CvOrder co) {
+    static_assert((long long)RPG * 8160 * 4080 < (1ll << 31), "a lane's partial sums must fit int32");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x;
     const int seq = blockIdx.y;
@@ -280,7 +281,9 @@ hipError_t launch_lk_cv(const LKBatch& b, int nseq, int max_n, const LKParams& l
     }
 #undef SVO_LK_CV_CASE
     if (rpg <= 16) return launch_cv_rpg<16>(b, nseq, max_n, d, st);
-    return launch_cv_rpg<32>(b, nseq, max_n, d, st);
+    if (rpg <= 32) return launch_cv_rpg<32>(b, nseq, max_n, d, st);
+    if (rpg <= 48) return launch_cv_rpg<48>(b, nseq, max_n, d, st);
+    return launch_cv_rpg<64>(b, nseq, max_n, d, st);
 }
 
 }  // namespace svo

@@ -11,8 +11,8 @@
 //    normal equations with one v_dot2_i32_i16 per sum (b1, b2, A11, A12, A22),
 //    replacing two quarter-rate v_mul_lo_u32 per pixel and sum.
 // All values fit int16 (|J - I| <= 8160, |Ix|, |Iy| <= 4080) and the per-lane
-// int32 sums cannot overflow (7 rows x 2 x 8160 x 4080 < 2^31), so the sums are
-// the same exact integers as before: bit-identical results.
+// int32 sums cannot overflow (at most 16 rows x 8160 x 4080 < 2^31), so the sums
+// are the same exact integers as before: bit-identical results.
 #include "lk_device.hpp"
 
 namespace svo {
@@ -34,11 +34,14 @@ struct Shape {
     static constexpr int WAVE_BYTES = IBYTES + JBYTES + 16;  // + a sink for the stager's spare lanes
 };
 
-// Exact wave sums of int32 values whose per-lane magnitude is below 2^31/8
-// (true for b1, b2, A11, A12, A22: <= RPG * 2 * 8160 * 4080): the first three
-// DPP steps (8-lane partial sums) run in int32, then each partial is split into
-// 16-bit halves for the last three steps, all chains interleaved so that no
-// DPP read waits on the write before it (no s_nop padding). The results are
+// Exact wave sums of int32 values. A lane's b1, b2, A11, A12, A22 are bounded by
+// RPG * 8160 * 4080 (RPG rows of |J - I| <= 8160 times |Ix| <= 4080): the first
+// S32 DPP steps (2^S32-lane partial sums) run in int32 -- three where eight
+// lanes' bound stays below 2^31 (strips of up to 8 rows: 11, 15 and 21 px), two
+// for the 16-row strips of 31 x 31, whose eight lanes reach 4.26e9 (steps32) --
+// then each partial is split into 16-bit halves for the remaining steps, all
+// chains interleaved so that no DPP read waits on the write before it (no s_nop
+// padding). The results are
 // the FLT_SCALE'd floats: hi * 65536 is exact in float (|hi| < 2^24) and the one
 // addition rounds the exact total once -- the same float as
 // (float)(double)(int64 total), without the int64 / double detour.
@@ -48,14 +51,26 @@ __device__ __forceinline__ float halves_to_float(int hi_lane, int lo_lane) {
     return (h * 65536.f + l) * FLT_SCALE;
 }
 
+constexpr int steps32(int rpg) { return 8ll * rpg * 8160 * 4080 < (1ll << 31) ? 3 : 2; }
+
+template <int S32>
 __device__ __forceinline__ void wave_sum_f2(int x, int y, float& fx, float& fy) {
+    static_assert(S32 == 2 || S32 == 3, "row_shr:4 in int32 or on the halves");
     x = dpp_add<0xb1, 0xf, true>(x);
     y = dpp_add<0xb1, 0xf, true>(y);
     x = dpp_add<0x4e, 0xf, true>(x);
     y = dpp_add<0x4e, 0xf, true>(y);
-    x = dpp_add<0x114, 0xf, true>(x);
-    y = dpp_add<0x114, 0xf, true>(y);
+    if (S32 == 3) {
+        x = dpp_add<0x114, 0xf, true>(x);
+        y = dpp_add<0x114, 0xf, true>(y);
+    }
     int xh = x >> 16, xl = x & 0xFFFF, yh = y >> 16, yl = y & 0xFFFF;
+    if (S32 == 2) {
+        xh = dpp_add<0x114, 0xf, true>(xh);
+        xl = dpp_add<0x114, 0xf, true>(xl);
+        yh = dpp_add<0x114, 0xf, true>(yh);
+        yl = dpp_add<0x114, 0xf, true>(yl);
+    }
     xh = dpp_add<0x118, 0xf, true>(xh);
     xl = dpp_add<0x118, 0xf, true>(xl);
     yh = dpp_add<0x118, 0xf, true>(yh);
@@ -73,17 +88,29 @@ __device__ __forceinline__ void wave_sum_f2(int x, int y, float& fx, float& fy) 
 }
 
 // three chains: the normal matrix (A11, A12, A22) in one pass
+template <int S32>
 __device__ __forceinline__ void wave_sum_f3(int x, int y, int z, float& fx, float& fy, float& fz) {
+    static_assert(S32 == 2 || S32 == 3, "row_shr:4 in int32 or on the halves");
     x = dpp_add<0xb1, 0xf, true>(x);
     y = dpp_add<0xb1, 0xf, true>(y);
     z = dpp_add<0xb1, 0xf, true>(z);
     x = dpp_add<0x4e, 0xf, true>(x);
     y = dpp_add<0x4e, 0xf, true>(y);
     z = dpp_add<0x4e, 0xf, true>(z);
-    x = dpp_add<0x114, 0xf, true>(x);
-    y = dpp_add<0x114, 0xf, true>(y);
-    z = dpp_add<0x114, 0xf, true>(z);
+    if (S32 == 3) {
+        x = dpp_add<0x114, 0xf, true>(x);
+        y = dpp_add<0x114, 0xf, true>(y);
+        z = dpp_add<0x114, 0xf, true>(z);
+    }
     int xh = x >> 16, xl = x & 0xFFFF, yh = y >> 16, yl = y & 0xFFFF, zh = z >> 16, zl = z & 0xFFFF;
+    if (S32 == 2) {
+        xh = dpp_add<0x114, 0xf, true>(xh);
+        xl = dpp_add<0x114, 0xf, true>(xl);
+        yh = dpp_add<0x114, 0xf, true>(yh);
+        yl = dpp_add<0x114, 0xf, true>(yl);
+        zh = dpp_add<0x114, 0xf, true>(zh);
+        zl = dpp_add<0x114, 0xf, true>(zl);
+    }
     xh = dpp_add<0x118, 0xf, true>(xh);
     xl = dpp_add<0x118, 0xf, true>(xl);
     yh = dpp_add<0x118, 0xf, true>(yh);
@@ -160,6 +187,8 @@ template <int WW, int WH>
 __global__ __launch_bounds__(256, 1) void lk_fast_kernel(LKBatch B, LKDev p) {
     using S = Shape<WW, WH>;
     constexpr int RPG = S::RPG, NP = S::NP;
+    constexpr int S32 = steps32(RPG);  // DPP steps of the wave sums that stay in int32
+    static_assert((1ll << S32) * RPG * 8160 * 4080 < (1ll << 31), "2^S32 lanes' partial sums must fit int32");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -306,7 +335,7 @@ __global__ __launch_bounds__(256, 1) void lk_fast_kernel(LKBatch B, LKDev p) {
             }
         }
         float A11, A12, A22;
-        wave_sum_f3(a11, a12, a22, A11, A12, A22);
+        wave_sum_f3<S32>(a11, a12, a22, A11, A12, A22);
 
         float D = A11 * A22 - A12 * A12;
         float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WW * WH);
@@ -351,7 +380,7 @@ __global__ __launch_bounds__(256, 1) void lk_fast_kernel(LKBatch B, LKDev p) {
                 }
             }
             float fb1, fb2;
-            wave_sum_f2(b1, b2, fb1, fb2);
+            wave_sum_f2<S32>(b1, b2, fb1, fb2);
             const float dx = (A12 * fb2 - A22 * fb1) * D;
             const float dy = (A12 * fb1 - A11 * fb2) * D;
             nextx += dx;

@@ -14,6 +14,7 @@ namespace {
 
 template <int RPG, bool FULL>
 __global__ __launch_bounds__(256) void lk_kernel(LKBatch B, LKDev p) {
+    static_assert((long long)RPG * 8160 * 4080 < (1ll << 31), "a lane's partial sums must fit int32");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -154,7 +155,10 @@ hipError_t launch_lk_generic(const LKBatch& b, int nseq, int max_n, const LKPara
     // uncommon strip heights: round up to the next instantiated size
     if (rpg <= 13) return launch_rpg<14>(b, nseq, max_n, d, st);
     if (rpg <= 16) return launch_rpg<16>(b, nseq, max_n, d, st);
-    return launch_rpg<32>(b, nseq, max_n, d, st);
+    if (rpg <= 32) return launch_rpg<32>(b, nseq, max_n, d, st);
+    // windows wider than 32 px: one strip per column, the window's height
+    if (rpg <= 48) return launch_rpg<48>(b, nseq, max_n, d, st);
+    return launch_rpg<64>(b, nseq, max_n, d, st);
 }
 
 }  // namespace svo

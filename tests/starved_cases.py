@@ -13,6 +13,7 @@ from types import SimpleNamespace
 import numpy as np
 
 import oracle as O
+from extreme_images import binarise
 from oracle_loop import OracleLoop
 from svo_amd.scene import Scene, SceneForward
 
@@ -25,9 +26,10 @@ W, H = 320, 240
 # SceneForward (translation, an occluder: RANSAC drops points every frame and the
 # keyframes add tens) instead of Scene; strips / strip: on the frames `strips` the
 # left `strip` columns of both images are constant (the features there are lost,
-# the others live on)
-Case = namedtuple("Case", "seed n frames drops side every blank bucket acc forward strips strip",
-                  defaults=((), "both", 0, False, (0, 0), O.ACC_EXACT, False, (), W // 2))
+# the others live on); binary: both images binarised (extreme_images.binarise: 255
+# where the frame is >= 128, else 0 -- the scene's geometry and motion at full contrast)
+Case = namedtuple("Case", "seed n frames drops side every blank bucket acc forward strips strip binary",
+                  defaults=((), "both", 0, False, (0, 0), O.ACC_EXACT, False, (), W // 2, False))
 
 LADDER = [Case(seed, n, 6) for seed in (2, 5) for n in range(1, 10)]
 DROPPED_64 = Case(4, 64, 9, drops=(3, 6))
@@ -38,6 +40,12 @@ STREAMED = Case(4, 64, 25, every=3)
 # a streamed run whose map fills while features live: five drops and rebuilds, then
 # every second frame loses the left 100 columns' features and the next replaces them
 RECLAIM = Case(3, 450, 25, drops=(2, 4, 6, 8, 10), strips=tuple(range(12, 24, 2)), strip=100)
+# binarised scenes (test_frontend_saturated_gpu.py): the two seeds of one batch
+SATURATED_SEEDS = (4, 2)
+
+
+def saturated(n, forward=False, **kw):
+    return [Case(seed, n, 7, binary=True, forward=forward, **kw) for seed in SATURATED_SEEDS]
 
 
 def blank_image():
@@ -68,6 +76,8 @@ def frames(case):
             L, R = L.copy(), R.copy()
             L[:, : case.strip] = 128
             R[:, : case.strip] = 128
+        if case.binary:
+            L, R = binarise(L), binarise(R)
         L.setflags(write=False)
         R.setflags(write=False)
         out.append((L, R))
@@ -163,3 +173,17 @@ def assert_reclaim_moves_live_points(case, n_frames=4, block=256):
     mid = oracle_trace(case)[first].mid[: o.n]
     assert np.all(np.diff(mid) > 0) and mid[-1] >= o.n  # strictly increasing, some point moves down
     return first
+
+
+def assert_saturated_conditions(cases):
+    """The oracle side of the binarised cases: every left frame is 0 / 255 with a
+    full-range edge (max |Scharr| = 4080), every step tracks at least 50 features,
+    and RANSAC keeps >= 0.9 of them on Scene, >= 0.6 on SceneForward."""
+    for case in cases:
+        for L, _ in frames(case):
+            assert set(np.unique(L)) <= {0, 255}
+            assert int(np.abs(O.scharr(L).astype(np.int32)).max()) == 4080
+        for s in oracle_trace(case)[1:]:
+            st = s.stats
+            assert st["tracked"] >= 50, (case, st)
+            assert st["inliers"] >= (0.6 if case.forward else 0.9) * st["tracked"], (case, st)
