@@ -166,14 +166,15 @@ int svo_fast_detect(svo_ctx* ctx, const svo_image* img, int threshold, int nonma
  * and corner flag, both W*H u8. */
 int svo_fast_score_map(svo_ctx* ctx, const svo_image* img, int threshold,
                        uint8_t* score, uint8_t* corner);
-/* ------------------------------------------------------------ ORB (detect only)
+/* ------------------------------------------------------------ ORB: detection
  * The reference's shipped default detector (use_orb: 1, R:configs/config.yaml:20-27):
  * cv::ORB::create(nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K,
  * scoreType, patchSize, fastThreshold) at R:src/tracking.cpp:33-50, used through
  * detect(img, keypoints, mask) at :82. Keypoints in OpenCV's order (level by level,
  * retainBest's order within a level), pt scaled to level 0; response = Harris (or
- * FAST) score; octave optional (may be NULL). Angles are not computed (the
- * reference keeps positions only, R:src/tracking.cpp:85). firstLevel must be 0. */
+ * FAST) score; octave optional (may be NULL). Angles are not computed here (the
+ * reference keeps positions only, R:src/tracking.cpp:85); svo_orb_compute below
+ * computes them with the descriptors. firstLevel must be 0. */
 #define SVO_ORB_HARRIS_SCORE 0
 #define SVO_ORB_FAST_SCORE 1
 typedef struct svo_orb_params {
@@ -182,7 +183,7 @@ typedef struct svo_orb_params {
     int nlevels;          /* 8 (<= 8) */
     int edge_threshold;   /* the reference passes patch_size (31) */
     int first_level;      /* 0 */
-    int wta_k;            /* 4 (descriptors only; unused by detect) */
+    int wta_k;            /* 4 in the reference; unused by detect; the descriptors support 2 only */
     int score_type;       /* SVO_ORB_HARRIS_SCORE */
     int patch_size;       /* 31 */
     int fast_threshold;   /* 20 */
@@ -198,6 +199,79 @@ int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* par
  * SVO_ERR_ARG: level outside [0, nlevels), or parameters svo_orb_detect rejects. */
 int svo_orb_level(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, const uint8_t* mask,
                   int level, uint8_t* out_img, uint8_t* out_mask, int* lw, int* lh);
+
+/* ------------------------------------------------------------ ORB: descriptors and matching
+ * Not in the reference (it only detects): where cv::ORB::compute / detectAndCompute
+ * and cv::BFMatcher(NORM_HAMMING)::knnMatch(k = 2) would stand in a port, for
+ * relocalisation against a map of described points. Every rule is stated in
+ * DESIGN.md section 3d and restated in numpy by tests/orb_describe_reference.py;
+ * parity with OpenCV's own bits is NOT pinned (its learned pattern is data the
+ * caller passes; its u8 GaussianBlur weights and its float cos/sin steering differ).
+ *
+ * For a keypoint (x, y, octave) as svo_orb_detect returns it, hp = patch_size / 2:
+ *   level pixel  cx = cvRound(x * (1.f / lscale[octave])) in f32, cy likewise
+ *   validity     reach = cvRound(hp sqrt 2); valid iff reach <= cx <= lw - 1 - reach and
+ *                the same for cy; else valid = 0, a zero descriptor, angle -1
+ *   moments      m10 = sum u I, m01 = sum v I on the UNBLURRED level over |v| <= hp,
+ *                |u| <= umax[|v|] (OpenCV's umax table), exact integers
+ *   direction    hyp = sqrt((double)(m10^2 + m01^2)), c = m10 / hyp, s = m01 / hyp in
+ *                f64 (c = 1, s = 0 without a gradient); angle = atan2(m01, m10) in
+ *                degrees [0, 360), informational only
+ *   blur         every level once, separable 7 taps {18,34,49,54,49,34,18} / 256,
+ *                REFLECT_101: h = sum w p, out = (sum w h + 32768) >> 16
+ *   steering     pattern point (px, py): ix = rint(px c - py s), iy = rint(px s + py c)
+ *                in f64, half to even; sample = blurred[cy + iy][cx + ix]
+ *   bits         WTA_K 2: bit j of byte i = sample(pattern[16i + 2j]) < sample(pattern[16i + 2j + 1])
+ * pattern_xy: 512 points (x, y) int8, each in [-hp, hp] (OpenCV's bit_pattern_31_
+ * for patch_size 31 if the caller has it), or NULL for svo_orb_default_pattern.
+ * SVO_ERR_ARG (nothing written): patch_size even or outside [5, 31], wta_k != 2,
+ * first_level != 0, a pattern entry outside [-hp, hp], an octave outside
+ * [0, nlevels), negative counts, parameters svo_orb_detect rejects. */
+#define SVO_ORB_DESC_BYTES 32
+/* OpenCV's pattern for patchSize != 31 (makeRandomPattern): cv::RNG(0x34985739),
+ * x = uniform(-hp, hp + 1) then y likewise, 512 points. Host only, no context. */
+int svo_orb_default_pattern(int patch_size, int8_t pattern_xy[1024]);
+/* Test view (host only): the hp + 1 entries of umax; writes min(hp + 1, cap), *n = hp + 1. */
+int svo_orb_umax(int patch_size, int* umax, int cap, int* n);
+/* desc n*32 bytes, angle n floats or NULL, valid n bytes. n = 0 is valid. */
+int svo_orb_compute(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, const int8_t* pattern_xy,
+                    const svo_keypoint* kp, const int* octave, int n, uint8_t* desc, float* angle, uint8_t* valid);
+/* svo_orb_detect, then svo_orb_compute of its keypoints on the same pyramid (built
+ * once). kp / octave / *n_out as svo_orb_detect writes them (octave and angle may be
+ * NULL); desc, angle, valid for the min(n, cap) keypoints written. */
+int svo_orb_detect_and_compute(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, const uint8_t* mask,
+                               const int8_t* pattern_xy, svo_keypoint* kp, int* octave, uint8_t* desc, float* angle,
+                               uint8_t* valid, int cap, int* n_out);
+/* Test view, as svo_orb_level: level `level` of the blurred pyramid the descriptors sample. */
+int svo_orb_blur_level(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, int level, uint8_t* out,
+                       int* lw, int* lh);
+/* Hamming 2-NN of 32-byte descriptors, n_problems independent problems: problem p
+ * matches queries q + p*q_stride*32 (nq[p] of them) against train t + p*t_stride*32
+ * (nt[p]). For query i of problem p, idx[(p*q_stride + i)*2 + k] and dist[...] hold
+ * the best (k = 0) and second-best (k = 1) train index and distance (popcount of
+ * the xor, 0..256) by strict < while the train index rises: ties go to the lowest
+ * index. A missing neighbour (nt[p] of 0 or 1) is idx -1, dist 257. Rows past nq[p]
+ * are not written. SVO_ERR_ARG: negative counts, a count above its stride, more
+ * than 65535 problems. n_problems = 0 is valid. */
+int svo_match_hamming(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_stride, int t_stride,
+                      const uint8_t* q, const uint8_t* t, int* idx, int* dist);
+/* Ratio test and cross-check on svo_match_hamming's output of one problem (host
+ * only, integers): keep (q, t = idx_qt[2q]) iff t >= 0, and (ratio_pct != 0)
+ * idx_qt[2q+1] >= 0 with dist1 * 100 < ratio_pct * dist2, and (idx_tq != NULL: the
+ * reverse match, nt rows) idx_tq[2t] == q. Pairs in ascending q; writes min(n, cap)
+ * pairs, *n_out = n. SVO_ERR_ARG (nothing written): negative counts or ratio, an
+ * index >= nt. */
+int svo_match_filter(const int* idx_qt, const int* dist_qt, int nq, const int* idx_tq, int nt, int ratio_pct,
+                     int* pairs, int cap, int* n_out);
+/* Measurement only (tools/orb_describe_bench.py): HIP-event time per launch, in ms,
+ * over `reps` back-to-back launches after a warm-up, no transfers. svo_orb_describe_time:
+ * detects up to cap keypoints of img (*n_kp), then ms[0] orb_blur_kernel (all levels),
+ * ms[1] orb_angle_kernel, ms[2] orb_brief_kernel on them, default pattern.
+ * svo_match_hamming_time: hamming_knn2_kernel on the uploaded problems. */
+int svo_orb_describe_time(svo_ctx* ctx, const svo_image* img, const svo_orb_params* params, int cap, int reps,
+                          double ms[3], int* n_kp);
+int svo_match_hamming_time(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_stride, int t_stride,
+                           const uint8_t* q, const uint8_t* t, int reps, double* ms);
 
 /* R:src/tracking.cpp:76-79: W*H mask of 255 with a filled box of +-half around
  * each point (cvRound corners, inclusive, clipped). Host output. */

@@ -17,6 +17,8 @@ svo_amd                            reference call site
 ``Context.calc_optical_flow_pyr_lk``  cv::calcOpticalFlowPyrLK, :101-105, :160-165
 ``Context.pnp_residuals``           PnPRansacCallback::computeError+findInliers
 ``Context.solve_pnp_ransac``        cv::solvePnPRansac(..., SQPNP), :191-196
+``Context.orb_detect_and_compute``  (not in the reference) cv::ORB::detectAndCompute
+``Context.match_hamming``           (not in the reference) BFMatcher::knnMatch(k = 2)
 =================================  ===========================================
 
 There is no CPU fallback: every compute call goes through the HIP kernels and
@@ -36,6 +38,7 @@ __all__ = [
     "TERM_COUNT", "TERM_EPS", "LK_USE_INITIAL_FLOW", "LK_GET_MIN_EIGENVALS", "LK_OPENCV_ORDER",
     "lib_path", "Frontend", "FrontendConfig", "FrontendStats",
     "RectMaps", "init_undistort_rectify_map", "remap", "StereoRowsParams", "STEREO_NO_PRIOR",
+    "OrbParams", "ORB_DESC_BYTES", "orb_default_pattern", "orb_umax", "match_filter",
 ]
 
 STEREO_NO_PRIOR = -(2 ** 31)  # SVO_STEREO_NO_PRIOR: a point of the guided row match without a prior
@@ -89,6 +92,7 @@ class SvoError(RuntimeError):
 _LIB = None
 
 _u8p = C.POINTER(C.c_uint8)
+_i8p = C.POINTER(C.c_int8)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int)
@@ -119,6 +123,16 @@ _SIGS = [
     ("svo_fast_detect", C.c_int, [_vp, _vp, C.c_int, C.c_int, _u8p, _f32p, C.c_int, _i32p]),
     ("svo_orb_detect", C.c_int, [_vp, _vp, _vp, _u8p, _f32p, _i32p, C.c_int, _i32p]),
     ("svo_orb_level", C.c_int, [_vp, _vp, _vp, _u8p, C.c_int, _u8p, _u8p, _i32p, _i32p]),
+    ("svo_orb_default_pattern", C.c_int, [C.c_int, _i8p]),
+    ("svo_orb_umax", C.c_int, [C.c_int, _i32p, C.c_int, _i32p]),
+    ("svo_orb_compute", C.c_int, [_vp, _vp, _vp, _i8p, _f32p, _i32p, C.c_int, _u8p, _f32p, _u8p]),
+    ("svo_orb_detect_and_compute", C.c_int, [_vp, _vp, _vp, _u8p, _i8p, _f32p, _i32p, _u8p, _f32p, _u8p, C.c_int,
+                                             _i32p]),
+    ("svo_orb_blur_level", C.c_int, [_vp, _vp, _vp, C.c_int, _u8p, _i32p, _i32p]),
+    ("svo_match_hamming", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u8p, _u8p, _i32p, _i32p]),
+    ("svo_match_filter", C.c_int, [_i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, C.c_int, _i32p]),
+    ("svo_orb_describe_time", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _f64p, _i32p]),
+    ("svo_match_hamming_time", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u8p, _u8p, C.c_int, _f64p]),
     ("svo_fast_score_map", C.c_int, [_vp, _vp, C.c_int, _u8p, _u8p]),
     ("svo_mask_boxes", C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_float, _u8p]),
     ("svo_bucket_features", C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -221,6 +235,50 @@ def solve_pnp_sqpnp(obj, img_pts, K):
     if rc < 0:
         raise SvoError(f"svo_solve_pnp_sqpnp: error {rc}")
     return rc == 1, rv, tv
+
+
+ORB_DESC_BYTES = 32  # SVO_ORB_DESC_BYTES
+
+
+def orb_default_pattern(patch_size: int = 31) -> np.ndarray:
+    """svo_orb_default_pattern: OpenCV's makeRandomPattern, (512, 2) int8 (x, y)
+    in [-patch_size // 2, patch_size // 2]. Host code of the library; no GPU context."""
+    out = np.empty((512, 2), np.int8)
+    if lib().svo_orb_default_pattern(int(patch_size), _p(out, _i8p)) != 0:
+        raise SvoError("svo_orb_default_pattern: patch_size must be odd and in [5, 31]")
+    return out
+
+
+def orb_umax(patch_size: int = 31) -> np.ndarray:
+    """svo_orb_umax (test view): the circular patch's half row widths, patch_size // 2 + 1 ints."""
+    out = np.empty(16, np.int32)
+    n = C.c_int()
+    if lib().svo_orb_umax(int(patch_size), _p(out, _i32p), 16, C.byref(n)) != 0:
+        raise SvoError("svo_orb_umax: patch_size must be odd and in [5, 31]")
+    return out[: n.value].copy()
+
+
+def match_filter(idx_qt, dist_qt, idx_tq=None, ratio_pct: int = 80, cap=None) -> np.ndarray:
+    """svo_match_filter: ratio test (ratio_pct 0 = off) and, with the reverse match
+    idx_tq, cross-check on match_hamming's output -> int32 (n, 2) pairs (q, t) in
+    ascending q; the first `cap` of them when cap is given. Host code; no GPU context."""
+    idx_qt = _c(idx_qt, np.int32).reshape(-1, 2)
+    dist_qt = _c(dist_qt, np.int32).reshape(-1, 2)
+    nq = len(idx_qt)
+    assert len(dist_qt) == nq
+    tq = None
+    nt = int(idx_qt.max()) + 1 if nq else 0
+    if idx_tq is not None:
+        tq = _c(idx_tq, np.int32).reshape(-1, 2)
+        nt = len(tq)
+    cap = nq if cap is None else int(cap)
+    pairs = np.empty((max(cap, 1), 2), np.int32)
+    n = C.c_int()
+    rc = lib().svo_match_filter(_p(idx_qt, _i32p), _p(dist_qt, _i32p), nq, None if tq is None else _p(tq, _i32p),
+                                max(nt, 0), int(ratio_pct), _p(pairs, _i32p), cap, C.byref(n))
+    if rc != 0:
+        raise SvoError("svo_match_filter: bad arguments (negative ratio, or an index past the reverse match)")
+    return pairs[: min(n.value, cap)].copy()
 
 
 class PinnedBuffer:
@@ -445,11 +503,11 @@ class OrbParams(C.Structure):
     HARRIS, FAST = 0, 1
 
     def __init__(self, nfeatures=150, scale_factor=1.2, nlevels=8, patch_size=31, fast_threshold=20,
-                 edge_threshold=None, score_type=0):
+                 edge_threshold=None, score_type=0, wta_k=4):
         super().__init__()
         self.nfeatures, self.scale_factor, self.nlevels = nfeatures, scale_factor, nlevels
         self.edge_threshold = patch_size if edge_threshold is None else edge_threshold
-        self.first_level, self.wta_k, self.score_type = 0, 4, score_type
+        self.first_level, self.wta_k, self.score_type = 0, wta_k, score_type
         self.patch_size, self.fast_threshold = patch_size, fast_threshold
 
 
@@ -577,6 +635,154 @@ class Context:
         n = lw.value * lh.value
         shape = (lh.value, lw.value)
         return out[:n].reshape(shape).copy(), None if om is None else om[:n].reshape(shape).copy()
+
+    # ---------------------------------------------------------------- ORB descriptors, matching
+    @staticmethod
+    def _pattern_arg(pattern):
+        if pattern is None:
+            return None, None
+        pattern = _c(pattern, np.int8)
+        if pattern.size != 1024:
+            raise SvoError("pattern: 512 points (x, y) int8 expected")
+        return pattern, _p(pattern, _i8p)
+
+    def orb_compute(self, img: Image, kp, octave, params: "OrbParams" = None, pattern=None):
+        """cv::ORB::compute by the rules of DESIGN.md section 3d (svo_orb_compute): kp
+        (n, 2) or (n, 3) level-0 coordinates and octave (n,) as orb_detect returns
+        them -> (desc (n, 32) u8, angle (n,) f32 degrees, valid (n,) bool). pattern:
+        (512, 2) int8 or None for orb_default_pattern(params.patch_size)."""
+        params = params or OrbParams(wta_k=2)
+        kp = np.asarray(kp, np.float32)
+        kp = kp.reshape(-1, kp.shape[-1] if kp.ndim == 2 else 2)
+        n = len(kp)
+        k3 = np.zeros((n, 3), np.float32)
+        k3[:, :2] = kp[:, :2]
+        octave = _c(octave, np.int32).reshape(-1)
+        if len(octave) != n:
+            raise SvoError("orb_compute: one octave per keypoint expected")
+        desc = np.zeros((n, ORB_DESC_BYTES), np.uint8)
+        angle = np.zeros(n, np.float32)
+        valid = np.zeros(n, np.uint8)
+        keep, pp = self._pattern_arg(pattern)
+        self._check(lib().svo_orb_compute(self.handle, img.handle, C.byref(params), pp, _p(k3, _f32p),
+                                          _p(octave, _i32p), n, _p(desc, _u8p), _p(angle, _f32p), _p(valid, _u8p)))
+        return desc, angle, valid.astype(bool)
+
+    def orb_detect_and_compute(self, img: Image, params: "OrbParams" = None, mask=None, pattern=None,
+                               cap: int = 1 << 16):
+        """cv::ORB::detectAndCompute (svo_orb_detect_and_compute; the pyramid is built
+        once) -> (kp (n, 3) f32, octave (n,) i32, desc (n, 32) u8, angle (n,) f32,
+        valid (n,) bool): orb_detect's keypoints with orb_compute's output."""
+        params = params or OrbParams(wta_k=2)
+        kp = np.empty((cap, 3), np.float32)
+        octv = np.empty(cap, np.int32)
+        desc = np.zeros((cap, ORB_DESC_BYTES), np.uint8)
+        angle = np.zeros(cap, np.float32)
+        valid = np.zeros(cap, np.uint8)
+        n = C.c_int()
+        mp = None
+        if mask is not None:
+            mask = _c(mask, np.uint8)
+            assert mask.shape == (img.h, img.w)
+            mp = _p(mask, _u8p)
+        keep, pp = self._pattern_arg(pattern)
+        self._check(lib().svo_orb_detect_and_compute(self.handle, img.handle, C.byref(params), mp, pp, _p(kp, _f32p),
+                                                     _p(octv, _i32p), _p(desc, _u8p), _p(angle, _f32p),
+                                                     _p(valid, _u8p), cap, C.byref(n)))
+        k = min(n.value, cap)
+        return kp[:k].copy(), octv[:k].copy(), desc[:k].copy(), angle[:k].copy(), valid[:k].astype(bool)
+
+    def orb_blur_level(self, img: Image, params: "OrbParams" = None, level: int = 0) -> np.ndarray:
+        """Test and debug only (svo_orb_blur_level): level `level` of the blurred
+        pyramid the descriptors sample."""
+        params = params or OrbParams(wta_k=2)
+        out = np.empty(img.h * img.w, np.uint8)  # no level is larger than level 0
+        lw, lh = C.c_int(), C.c_int()
+        self._check(lib().svo_orb_blur_level(self.handle, img.handle, C.byref(params), int(level), _p(out, _u8p),
+                                             C.byref(lw), C.byref(lh)))
+        return out[: lw.value * lh.value].reshape(lh.value, lw.value).copy()
+
+    def match_hamming(self, q, t, nq=None, nt=None, idx=None, dist=None):
+        """cv::BFMatcher(NORM_HAMMING)::knnMatch(k = 2) (svo_match_hamming), ties to the
+        lowest train index. Single sets: q (nq, 32), t (nt, 32) u8 -> (idx (nq, 2) i32,
+        dist (nq, 2) i32), best then second best; a missing neighbour is (-1, 257).
+        Batched: q (P, q_stride, 32), t (P, t_stride, 32) with counts nq (P,), nt (P,)
+        -> (P, q_stride, 2) arrays whose rows past nq[p] keep what idx / dist (given,
+        int32, written in place) held, or (-1, 257) without them."""
+        q = _c(q, np.uint8)
+        t = _c(t, np.uint8)
+        if nq is None and nt is None:
+            q = q.reshape(-1, ORB_DESC_BYTES)
+            t = t.reshape(-1, ORB_DESC_BYTES)
+            P, qs, ts = 1, len(q), len(t)
+            nq_a, nt_a = np.array([qs], np.int32), np.array([ts], np.int32)
+            shape = (qs, 2)
+        else:
+            if q.ndim != 3 or t.ndim != 3 or q.shape[2] != ORB_DESC_BYTES or t.shape[2] != ORB_DESC_BYTES or \
+                    len(q) != len(t) or nq is None or nt is None:
+                raise SvoError("match_hamming: batched form takes q (P, q_stride, 32), t (P, t_stride, 32), nq, nt")
+            P, qs, ts = len(q), q.shape[1], t.shape[1]
+            nq_a, nt_a = _c(nq, np.int32).reshape(-1), _c(nt, np.int32).reshape(-1)
+            if len(nq_a) != P or len(nt_a) != P:
+                raise SvoError("match_hamming: one count per problem expected")
+            shape = (P, qs, 2)
+        if idx is None:
+            idx = np.full(shape, -1, np.int32)
+        if dist is None:
+            dist = np.full(shape, 257, np.int32)
+        if idx.dtype != np.int32 or dist.dtype != np.int32 or idx.shape != shape or dist.shape != shape or \
+                not idx.flags.c_contiguous or not dist.flags.c_contiguous:
+            raise SvoError(f"match_hamming: idx / dist must be C-contiguous int32 of shape {shape}")
+        self._check(lib().svo_match_hamming(self.handle, P, _p(nq_a, _i32p), _p(nt_a, _i32p), qs, ts, _p(q, _u8p),
+                                            _p(t, _u8p), _p(idx, _i32p), _p(dist, _i32p)))
+        return idx, dist
+
+    def orb_describe_time(self, img: Image, params: "OrbParams" = None, cap: int = 1 << 16, reps: int = 20):
+        """Measurement only (svo_orb_describe_time): ms per launch of the blur, angle and
+        BRIEF kernels on img's detected keypoints -> (ms (3,), keypoints)."""
+        params = params or OrbParams(wta_k=2)
+        ms = np.zeros(3, np.float64)
+        n = C.c_int()
+        self._check(lib().svo_orb_describe_time(self.handle, img.handle, C.byref(params), int(cap), int(reps),
+                                                _p(ms, _f64p), C.byref(n)))
+        return ms, n.value
+
+    def match_hamming_time(self, q, t, nq, nt, reps: int = 10) -> float:
+        """Measurement only (svo_match_hamming_time): ms per launch of the matcher on
+        the batch q (P, q_stride, 32), t (P, t_stride, 32) with counts nq, nt."""
+        q = _c(q, np.uint8)
+        t = _c(t, np.uint8)
+        nq_a, nt_a = _c(nq, np.int32).reshape(-1), _c(nt, np.int32).reshape(-1)
+        assert q.ndim == 3 and t.ndim == 3 and len(q) == len(t) == len(nq_a) == len(nt_a)
+        ms = C.c_double()
+        self._check(lib().svo_match_hamming_time(self.handle, len(q), _p(nq_a, _i32p), _p(nt_a, _i32p), q.shape[1],
+                                                 t.shape[1], _p(q, _u8p), _p(t, _u8p), int(reps), C.byref(ms)))
+        return ms.value
+
+    def relocalize(self, map_desc, map_xyz, desc, kp_xy, K, ratio_pct: int = 80, cross_check: bool = True,
+                   iterations: int = 100, reproj_err: float = 8.0, confidence: float = 0.999):
+        """Pose of a described frame against a described map: match_hamming of the
+        frame's descriptors (queries) against the map's and, with cross_check, the
+        reverse; match_filter; solve_pnp_ransac on the surviving pairs -> (rvec, tvec,
+        inlier pairs (m, 2) of (frame index, map index)). SvoError when fewer than 4
+        pairs survive or RANSAC finds no model."""
+        map_desc = _c(map_desc, np.uint8).reshape(-1, ORB_DESC_BYTES)
+        desc = _c(desc, np.uint8).reshape(-1, ORB_DESC_BYTES)
+        map_xyz = _c(map_xyz, np.float64).reshape(-1, 3)
+        kp_xy = np.asarray(kp_xy, np.float32)
+        kp_xy = _c(kp_xy.reshape(len(desc), -1)[:, :2], np.float32)
+        if len(map_xyz) != len(map_desc):
+            raise SvoError("relocalize: one map point per map descriptor expected")
+        idx_qt, dist_qt = self.match_hamming(desc, map_desc)
+        idx_tq = self.match_hamming(map_desc, desc)[0] if cross_check else None
+        pairs = match_filter(idx_qt, dist_qt, idx_tq, ratio_pct)
+        if len(pairs) < 4:
+            raise SvoError(f"relocalize: {len(pairs)} matches survive the filter, 4 needed")
+        ok, rvec, tvec, inl = self.solve_pnp_ransac(map_xyz[pairs[:, 1]], kp_xy[pairs[:, 0]], K, iterations,
+                                                    reproj_err, confidence)
+        if not ok:
+            raise SvoError("relocalize: RANSAC found no pose")
+        return rvec, tvec, pairs[inl]
 
     def fast_score_map(self, img: Image, threshold: int = 20):
         score = np.empty((img.h, img.w), np.uint8)

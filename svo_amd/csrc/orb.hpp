@@ -50,6 +50,51 @@ hipError_t orb_batch_detect(OrbBatch* ob, const ImgLevel* lv0, const float* box_
                             hipStream_t st, const std::function<void(int, const std::function<void(int)>&)>& par,
                             int* overflow);
 
+// svo_orb_detect's workspace (scratch slot 10) and the scale and mask pyramids built in it
+struct OrbLevels {
+    OrbGeometry g;
+    size_t mask_off[kMaxLevels];
+    PyrDesc lev;             // the levels (level 0 = the caller's image)
+    uint8_t* dmask;          // level masks at mask_off[l] (rows of lw[l]); null without a mask
+    PyrDesc* ddesc;          // device: [l].lv[0] = level l
+    unsigned long long* bits;
+    int *rowcnt, *rowoff;
+    svo_keypoint* dkp;       // [nlev][maxcap]
+    int* dn;
+    float* dresp;            // [nlev][maxcap]
+};
+// The two halves of svo_orb_detect (orb_detect.cpp), shared with svo_orb_level
+// and the descriptor entry points (orb_describe.cpp): the pyramids queued on the
+// context's stream, then detection and selection on them (synchronous).
+int orb_build_levels(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
+                     const char* who, OrbLevels& o);
+int orb_detect_levels(svo_ctx* ctx, const svo_orb_params* prm, OrbLevels& o, svo_keypoint* out, int* octave, int cap,
+                      int* n_out);
+
+// ORB descriptors (orb_describe.hip; the rules: DESIGN.md section 3d).
+constexpr int kOrbPatternPoints = 512;
+// One keypoint as the kernels take it: the level pixel, or level < 0 for a
+// keypoint too close to its level's border (zero descriptor, angle -1).
+struct OrbDescKp {
+    int cx, cy, level, pad;
+};
+struct OrbDirection {  // c = m10 / hyp, s = m01 / hyp (1, 0 without a gradient)
+    double c, s;
+};
+// every level of `levels` blurred into the level of the same size of `blurred`
+hipError_t launch_orb_blur(const PyrDesc& levels, const PyrDesc& blurred, hipStream_t st);
+// hp: half patch; umax: hp + 1 ints on the device
+hipError_t launch_orb_angle(const PyrDesc& levels, const OrbDescKp* kp, int n, int hp, const int* umax,
+                            OrbDirection* dir, float* angle, hipStream_t st);
+// blurred: the levels of launch_orb_blur as a PyrDesc; pattern: 512 (x, y) int8 on
+// the device; reach: the clamp of a steered offset (never binding, see the kernel)
+hipError_t launch_orb_brief(const PyrDesc& blurred, const OrbDescKp* kp, int n, const int8_t* pattern,
+                            const OrbDirection* dir, int reach, uint8_t* desc, hipStream_t st);
+// Hamming 2-NN (match.hip): problem p (blockIdx.y) matches queries q + p*q_stride*32
+// (nq[p] of them) against train t + p*t_stride*32 (nt[p]); idx / dist [p][q_stride][2]
+hipError_t launch_hamming_knn2(const uint32_t* q, const uint32_t* t, const int* nq, const int* nt, int q_stride,
+                               int t_stride, int n_problems, int max_nq, int* idx, int* dist, hipStream_t st);
+
 hipError_t launch_orb_resize(const uint8_t* src, int spitch, const uint8_t* smask, int sw, uint8_t* dst, int dpitch,
                              uint8_t* dmask, int dw, int dh, const int* xofs, const uint32_t* xc, const int* yofs,
                              const uint32_t* yc, hipStream_t st);

@@ -22,8 +22,9 @@
 // standard library's introselect leaves, so it runs on the host with the same
 // algorithms (a few thousand records per level) rather than being re-derived
 // on the GPU. n_l: nfeatures (1 - 1/f) / (1 - (1/f)^nlevels) rounded per level,
-// the rest to the last level. Keypoint angles (ICAngle) are not computed: the
-// reference converts keypoints to points (KeyPoint::convert) right away.
+// the rest to the last level. Keypoint angles (ICAngle) are not computed here: the
+// reference converts keypoints to points (KeyPoint::convert) right away;
+// svo_orb_compute (orb_describe.cpp) computes them with the descriptors.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -388,23 +389,7 @@ hipError_t orb_batch_detect(OrbBatch* ob, const ImgLevel* lv0, const float* box_
 
 }  // namespace svo
 
-using namespace svo;
-
-namespace {
-
-// svo_orb_detect's workspace and the scale and mask pyramids built in it
-struct OrbLevels {
-    OrbGeometry g;
-    size_t mask_off[kMaxLevels];
-    PyrDesc lev;             // the levels (level 0 = the caller's image)
-    uint8_t* dmask;          // level masks at mask_off[l] (rows of lw[l]); null without a mask
-    PyrDesc* ddesc;          // device: [l].lv[0] = level l
-    unsigned long long* bits;
-    int *rowcnt, *rowoff;
-    svo_keypoint* dkp;       // [nlev][maxcap]
-    int* dn;
-    float* dresp;            // [nlev][maxcap]
-};
+namespace svo {
 
 // The pyramid half of svo_orb_detect, shared with svo_orb_level: level geometry,
 // workspace layout, upload of the coefficient tables, the level descriptors and
@@ -489,7 +474,9 @@ int orb_build_levels(svo_ctx* ctx, const svo_image* img, const svo_orb_params* p
     return SVO_OK;
 }
 
-}  // namespace
+}  // namespace svo
+
+using namespace svo;
 
 extern "C" int svo_orb_level(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
                              int level, uint8_t* out_img, uint8_t* out_mask, int* lw, int* lh) {
@@ -510,13 +497,11 @@ extern "C" int svo_orb_level(svo_ctx* ctx, const svo_image* img, const svo_orb_p
     return SVO_OK;
 }
 
-extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
-                              svo_keypoint* out, int* octave, int cap, int* n_out) {
-    if (!ctx || !img || !prm || (!out && cap > 0) || cap < 0)
-        return set_error(ctx, SVO_ERR_ARG, "svo_orb_detect: bad arguments");
-    OrbLevels o;
-    const int rc = orb_build_levels(ctx, img, prm, mask, "svo_orb_detect", o);
-    if (rc != SVO_OK) return rc;
+namespace svo {
+
+// The detection half of svo_orb_detect on levels orb_build_levels has queued.
+int orb_detect_levels(svo_ctx* ctx, const svo_orb_params* prm, OrbLevels& o, svo_keypoint* out, int* octave, int cap,
+                      int* n_out) {
     hipStream_t st = ctx->stream;
     const OrbGeometry& g = o.g;
     const int nlev = g.nlev, maxcap = g.maxcap;
@@ -568,4 +553,16 @@ extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_
     const int n = orb_select(g, *prm, kp, rp, hn, out, octave, cap);
     if (n_out) *n_out = n;
     return SVO_OK;
+}
+
+}  // namespace svo
+
+extern "C" int svo_orb_detect(svo_ctx* ctx, const svo_image* img, const svo_orb_params* prm, const uint8_t* mask,
+                              svo_keypoint* out, int* octave, int cap, int* n_out) {
+    if (!ctx || !img || !prm || (!out && cap > 0) || cap < 0)
+        return set_error(ctx, SVO_ERR_ARG, "svo_orb_detect: bad arguments");
+    OrbLevels o;
+    const int rc = orb_build_levels(ctx, img, prm, mask, "svo_orb_detect", o);
+    if (rc != SVO_OK) return rc;
+    return orb_detect_levels(ctx, prm, o, out, octave, cap, n_out);
 }
