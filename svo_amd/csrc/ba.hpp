@@ -98,8 +98,8 @@ struct BaStageOut {
     float* our = nullptr;  // written where the lists carry ur and this is not null
 };
 int ba_stage_blocks(int W, int cap);
-size_t ba_stage_work_bytes(int P, int W, int cap);
-BaStageWork ba_stage_carve(void* mem, int P, int W, int cap);
+// the layout of that memory (layout.hpp): w's arrays from c
+void ba_stage_layout(Carver& c, int P, int W, int cap, BaStageWork& w);
 // pass 1: every observation's staged position and the counts n_points / n_obs
 hipError_t launch_ba_stage_place(const BaLists& l, const BaStageWork& w, hipStream_t st);
 // pass 2: the observations into (point, camera) order, the index lists per point

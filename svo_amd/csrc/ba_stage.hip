@@ -238,32 +238,14 @@ bool lists_ok(const BaLists& l) { return l.P > 0 && l.W > 0 && l.W <= kMaxCams &
 
 int ba_stage_blocks(int W, int cap) { return (W * cap + kPlaceBlock - 1) / kPlaceBlock; }
 
-namespace {
-size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-}  // namespace
-
-size_t ba_stage_work_bytes(int P, int W, int cap) {
+void ba_stage_layout(Carver& c, int P, int W, int cap, BaStageWork& w) {
     const size_t n = (size_t)P * W * cap;
-    return 3 * up256(sizeof(int) * n) + up256(sizeof(int) * (size_t)P * ba_stage_blocks(W, cap)) +
-           2 * up256(sizeof(int) * (size_t)P) + 256;
-}
-
-BaStageWork ba_stage_carve(void* mem, int P, int W, int cap) {
-    char* d = (char*)(((uintptr_t)mem + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t count) {
-        int* r = (int*)d;
-        d += up256(sizeof(int) * count);
-        return r;
-    };
-    const size_t n = (size_t)P * W * cap;
-    BaStageWork w;
-    w.pos = take(n);
-    w.flag = take(n);
-    w.smid = take(n);
-    w.part = take((size_t)P * ba_stage_blocks(W, cap));
-    w.n_points = take(P);
-    w.n_obs = take(P);
-    return w;
+    w.pos = c.take<int>(n);
+    w.flag = c.take<int>(n);
+    w.smid = c.take<int>(n);
+    w.part = c.take<int>((size_t)P * ba_stage_blocks(W, cap));
+    w.n_points = c.take<int>(P);
+    w.n_obs = c.take<int>(P);
 }
 
 hipError_t launch_ba_stage_place(const BaLists& l, const BaStageWork& w, hipStream_t st) {

@@ -106,23 +106,7 @@ int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bo
     const size_t P = (size_t)a.P, nC = P * a.maxC, nM = P * a.maxM, nO = P * a.maxO;
     s.nblk = ba_point_blocks(a.maxM);
     const size_t ld = 6 * (size_t)a.maxC;
-    const size_t dbl = 2 * 12 * nC + 2 * 3 * nM + kBaNE * nC + 6 * nM + 3 * nM + 6 * nM + 6 * nC +
-                       2 * P * s.nblk + 2 * P + nC + 3 * P + (want_S ? P * ld * ld + P * ld : 0) +
-                       (want_dp ? 3 * nM : 0);
-    const size_t ints = 2 * P + 3 * nO + P * (a.maxM + 1) + P * (a.maxC + 1) + nC + nM + 4 * P + (want_ids ? nM : 0);
     const bool stereo = a.baseline > 0;
-    const size_t bytes =
-        sizeof(double) * dbl + sizeof(int) * ints + sizeof(float) * (stereo ? 3 : 2) * nO + nC + 64 * 256;
-    char* d = (char*)scratch(ctx, 11, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    auto carve = [&](size_t n) {
-        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
-        char* r = d;
-        d += n;
-        return r;
-    };
-    auto dd = [&](size_t n) { return (double*)carve(sizeof(double) * n); };
-    auto di = [&](size_t n) { return (int*)carve(sizeof(int) * n); };
     BaBatch& b = s.b;
     b.P = a.P;
     b.maxC = a.maxC;
@@ -133,54 +117,45 @@ int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bo
     b.cx = K[2];
     b.cy = K[5];
     b.delta = delta;
-    s.poses = dd(12 * nC);
-    s.tposes = dd(12 * nC);
-    s.points = dd(3 * nM);
-    s.tpoints = dd(3 * nM);
-    b.cam_ne = dd(kBaNE * nC);
-    b.pt_V = dd(6 * nM);
-    b.pt_g = dd(3 * nM);
-    b.pt_Vinv = dd(6 * nM);
-    b.dc = dd(6 * nC);
-    b.step_part = dd(2 * P * s.nblk);
-    b.stepinfo = dd(2 * P);
-    b.cam_cost = dd(nC);
-    s.cost = dd(P);
-    s.tcost = dd(P);
-    s.lambda = dd(P);
-    s.S = want_S ? dd(P * ld * ld) : nullptr;
-    s.bvec = want_S ? dd(P * ld) : nullptr;
-    s.dp = want_dp ? dd(3 * nM) : nullptr;
-    s.n_cams = di(P);
-    s.n_points = di(P);
-    s.ocam = di(nO);
-    s.cam_idx = di(nO);
-    s.cam_pt = di(nO);
-    s.pt_off = di(P * (a.maxM + 1));
-    s.cam_off = di(P * (a.maxC + 1));
-    b.cam_cnt = di(nC);
-    b.pt_free = di(nM);
-    b.status = di(P);
-    b.n_free = di(P);
-    s.active = di(P);
-    s.accept = di(P);
-    s.pt_id = want_ids ? di(nM) : nullptr;
-    s.oxy = (float*)carve(sizeof(float) * 2 * nO);
-    s.fixed = (uint8_t*)carve(nC);
-    s.our = stereo ? (float*)carve(sizeof(float) * nO) : nullptr;
-    b.our = s.our;
+    auto layout = [&](Carver& c) {
+        s.poses = c.take<double>(12 * nC);
+        s.tposes = c.take<double>(12 * nC);
+        s.points = c.take<double>(3 * nM);
+        s.tpoints = c.take<double>(3 * nM);
+        b.cam_ne = c.take<double>(kBaNE * nC);
+        b.pt_V = c.take<double>(6 * nM);
+        b.pt_g = c.take<double>(3 * nM);
+        b.pt_Vinv = c.take<double>(6 * nM);
+        b.dc = c.take<double>(6 * nC);
+        b.step_part = c.take<double>(2 * P * s.nblk);
+        b.stepinfo = c.take<double>(2 * P);
+        b.cam_cost = c.take<double>(nC);
+        s.cost = c.take<double>(P);
+        s.tcost = c.take<double>(P);
+        b.lambda = s.lambda = c.take<double>(P);
+        s.S = want_S ? c.take<double>(P * ld * ld) : nullptr;
+        s.bvec = want_S ? c.take<double>(P * ld) : nullptr;
+        s.dp = want_dp ? c.take<double>(3 * nM) : nullptr;
+        b.n_cams = s.n_cams = c.take<int>(P);
+        b.n_points = s.n_points = c.take<int>(P);
+        b.ocam = s.ocam = c.take<int>(nO);
+        b.cam_idx = s.cam_idx = c.take<int>(nO);
+        b.cam_pt = s.cam_pt = c.take<int>(nO);
+        b.pt_off = s.pt_off = c.take<int>(P * (a.maxM + 1));
+        b.cam_off = s.cam_off = c.take<int>(P * (a.maxC + 1));
+        b.cam_cnt = c.take<int>(nC);
+        b.pt_free = c.take<int>(nM);
+        b.status = c.take<int>(P);
+        b.n_free = c.take<int>(P);
+        b.active = s.active = c.take<int>(P);
+        s.accept = c.take<int>(P);
+        s.pt_id = want_ids ? c.take<int>(nM) : nullptr;
+        b.oxy = s.oxy = c.take<float>(2 * nO);
+        b.fixed = s.fixed = c.take<uint8_t>(nC);
+        b.our = s.our = stereo ? c.take<float>(nO) : nullptr;
+    };
+    if (!carve_scratch(ctx, kScratchBa, layout)) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     b.baseline = a.baseline;
-    b.n_cams = s.n_cams;
-    b.n_points = s.n_points;
-    b.ocam = s.ocam;
-    b.cam_idx = s.cam_idx;
-    b.cam_pt = s.cam_pt;
-    b.pt_off = s.pt_off;
-    b.cam_off = s.cam_off;
-    b.oxy = s.oxy;
-    b.fixed = s.fixed;
-    b.lambda = s.lambda;
-    b.active = s.active;
     if (s.S) {
         SVO_HIP(ctx, hipMemsetAsync(s.S, 0, sizeof(double) * P * ld * ld, ctx->stream));
         SVO_HIP(ctx, hipMemsetAsync(s.bvec, 0, sizeof(double) * P * ld, ctx->stream));
@@ -371,11 +346,10 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, const std::vector<uint8_
     return SVO_OK;
 }
 
-// The staging chain's own memory (scratch slot 12: the LM's block lives in 11).
+// The staging chain's own memory (a slot of its own: the LM's block lives beside it).
 int stage_work(svo_ctx* ctx, const BaLists& l, BaStageWork& w) {
-    void* d = scratch(ctx, 12, ba_stage_work_bytes(l.P, l.W, l.cap));
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    w = ba_stage_carve(d, l.P, l.W, l.cap);
+    if (!carve_scratch(ctx, kScratchBaStage, [&](Carver& c) { ba_stage_layout(c, l.P, l.W, l.cap, w); }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     return SVO_OK;
 }
 
@@ -393,22 +367,25 @@ const char* check_lists(int P, int W, int cap, const int* counts, const int* ids
     return nullptr;
 }
 
-// ... and uploaded as they are (scratch slot 9)
+// ... and uploaded as they are
 int upload_lists(svo_ctx* ctx, int P, int W, int cap, const int* counts, const int* ids, const float* xy, BaLists& l,
                  const float* ur = nullptr) {
     const size_t nL = (size_t)P * W, nO = nL * cap;
-    char* in = (char*)scratch(ctx, 9, sizeof(int) * (nL + nO) + sizeof(float) * (ur ? 3 : 2) * nO + 1024);
-    if (!in) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    int* d_counts = (int*)in;
-    int* d_ids = (int*)(in + ((sizeof(int) * nL + 255) & ~(size_t)255));
-    float* d_xy = (float*)((char*)d_ids + ((sizeof(int) * nO + 255) & ~(size_t)255));
+    int *d_counts, *d_ids;
+    float *d_xy, *d_ur;
+    if (!carve_scratch(ctx, kScratchBaLists, [&](Carver& c) {
+            d_counts = c.take<int>(nL);
+            d_ids = c.take<int>(nO);
+            d_xy = c.take<float>(2 * nO);
+            d_ur = ur ? c.take<float>(nO) : nullptr;
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     hipStream_t st = ctx->stream;
     SVO_HIP(ctx, hipMemcpyAsync(d_counts, counts, sizeof(int) * nL, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(d_ids, ids, sizeof(int) * nO, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * nO, hipMemcpyHostToDevice, st));
     l = BaLists{P, W, cap, nullptr, d_counts, d_ids, d_xy};
     if (ur) {
-        float* d_ur = (float*)((char*)d_xy + ((sizeof(float) * 2 * nO + 255) & ~(size_t)255));
         SVO_HIP(ctx, hipMemcpyAsync(d_ur, ur, sizeof(float) * nO, hipMemcpyHostToDevice, st));
         l.ur = d_ur;
     }

@@ -26,7 +26,7 @@ int set_error(svo_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-void* scratch(svo_ctx* ctx, int slot, size_t bytes) {
+void* scratch(svo_ctx* ctx, ScratchSlot slot, size_t bytes) {
     svo_scratch& s = ctx->s[slot];
     if (s.bytes >= bytes && s.p) return s.p;
     if (s.p) {
@@ -77,7 +77,7 @@ int ingest_bgr(svo_ctx* ctx, const uint8_t* bgr, int stride, int w, int h, uint8
     }
     uint8_t* hb = (uint8_t*)ctx->ingest_host[i];
     for (int y = 0; y < h; y++) std::memcpy(hb + (size_t)y * bp, bgr + (size_t)y * stride, (size_t)3 * w);
-    uint8_t* dev = (uint8_t*)scratch(ctx, 8 + i, bytes);
+    uint8_t* dev = (uint8_t*)scratch(ctx, i ? kScratchIngest1 : kScratchIngest0, bytes);
     if (!dev) return set_error(ctx, SVO_ERR_HIP, "ingest: scratch alloc failed");
     SVO_HIP(ctx, hipMemcpyAsync(dev, hb, bytes, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipEventRecord(ctx->ingest_ev[i], ctx->stream));
@@ -85,7 +85,8 @@ int ingest_bgr(svo_ctx* ctx, const uint8_t* bgr, int stride, int w, int h, uint8
     return SVO_OK;
 }
 
-// Upload one pyramid descriptor to device scratch slot 3's head (single-image calls).
+// Upload one pyramid descriptor to `dst`, a member of the caller's scratch block
+// (single-image calls).
 static PyrDesc* stage_desc(svo_ctx* ctx, const svo_image* img, void* dst) {
     PyrDesc* h = (PyrDesc*)pinned(ctx, sizeof(PyrDesc));
     if (!h || hipStreamSynchronize(ctx->stream) != hipSuccess) return nullptr;
@@ -235,7 +236,7 @@ int svo_image_upload_bgr(svo_ctx* ctx, svo_image* img, const uint8_t* bgr, int s
     return svo_image_build_pyramid(ctx, img);
 }
 
-// A raw host frame into scratch slot 13 (a descriptor slot, then the frame's bytes
+// A raw host frame into its scratch block (a descriptor, then the frame's bytes
 // up to the end of its last row) and the rectifying kernel from there into level
 // 0 of `img` (device rows), on ctx->stream.
 static int rectify_from_host(svo_ctx* ctx, const uint8_t* raw, int stride, int bgr, const svo_rect_maps* maps,
@@ -243,14 +244,17 @@ static int rectify_from_host(svo_ctx* ctx, const uint8_t* raw, int stride, int b
     const RectMapsDev& m = maps->dev;
     const size_t bytes = (size_t)(m.raw_h - 1) * stride + (size_t)(bgr ? 3 : 1) * m.raw_w;
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the slot's last user is done
-    char* d = (char*)scratch(ctx, 13, 256 + bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "rectify: scratch alloc failed");
-    static_assert(sizeof(PyrDesc) <= 256, "descriptor slot");
-    const PyrDesc* dd = stage_desc(ctx, img, d);
-    if (!dd) return set_error(ctx, SVO_ERR_HIP, "rectify: descriptor staging failed");
-    SVO_HIP(ctx, hipMemcpyAsync(d + 256, raw, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PyrDesc* dd;
+    uint8_t* draw;
+    if (!carve_scratch(ctx, kScratchRectify, [&](Carver& c) {
+            dd = c.take<PyrDesc>(1);
+            draw = c.take<uint8_t>(bytes);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "rectify: scratch alloc failed");
+    if (!stage_desc(ctx, img, dd)) return set_error(ctx, SVO_ERR_HIP, "rectify: descriptor staging failed");
+    SVO_HIP(ctx, hipMemcpyAsync(draw, raw, bytes, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `raw` is the caller's again
-    SVO_HIP(ctx, launch_rectify_batched((const uint8_t*)d + 256, 0, stride, m, dd, 1, bgr != 0, ctx->stream));
+    SVO_HIP(ctx, launch_rectify_batched(draw, 0, stride, m, dd, 1, bgr != 0, ctx->stream));
     return SVO_OK;
 }
 
@@ -316,8 +320,15 @@ int svo_image_scharr_level(svo_ctx* ctx, const svo_image* img, int level, int16_
     size_t doff[kMaxLevels];
     int dpitch[kMaxLevels];
     const size_t dbytes = deriv_layout(img->w, img->h, nl, doff, dpitch);
-    char* d = (char*)scratch(ctx, 8, dbytes + 1024);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    PyrDesc* ddesc;
+    DerivDesc* dder;
+    char* dbase;
+    if (!carve_scratch(ctx, kScratchScharr, [&](Carver& c) {
+            ddesc = c.take<PyrDesc>(1);
+            dder = c.take<DerivDesc>(1);
+            dbase = c.take<char>(dbytes);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     struct Staged {
         PyrDesc pd;
         DerivDesc dd;
@@ -325,15 +336,11 @@ int svo_image_scharr_level(svo_ctx* ctx, const svo_image* img, int level, int16_
     Staged* hs = (Staged*)pinned(ctx, sizeof(Staged));
     if (!hs) return set_error(ctx, SVO_ERR_HIP, "pinned alloc");
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pinned staging is reused
-    char* dbase = d + 512;
     hs->pd = img->desc;
     for (int l = 0; l < kMaxLevels; l++) {
         hs->dd.data[l] = l < nl ? (uint32_t*)(dbase + doff[l]) : nullptr;
         hs->dd.pitch[l] = l < nl ? dpitch[l] : 0;
     }
-    PyrDesc* ddesc = (PyrDesc*)d;
-    DerivDesc* dder = (DerivDesc*)(d + 256);
-    static_assert(sizeof(PyrDesc) <= 256 && sizeof(DerivDesc) <= 256, "staging slots");
     SVO_HIP(ctx, hipMemcpyAsync(ddesc, &hs->pd, sizeof(PyrDesc), hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dder, &hs->dd, sizeof(DerivDesc), hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemsetAsync(dbase, 0, dbytes, ctx->stream));
@@ -349,10 +356,14 @@ int svo_fast_score_map(svo_ctx* ctx, const svo_image* img, int threshold, uint8_
     threshold = threshold < 0 ? 0 : threshold > 255 ? 255 : threshold;
     const ImgLevel& L = img->desc.lv[0];
     size_t npx = (size_t)L.w * L.h;
-    uint16_t* cs = (uint16_t*)scratch(ctx, 0, npx * 2 + 1024);
-    if (!cs) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    PyrDesc* dd = stage_desc(ctx, img, (char*)cs + ((npx * 2 + 255) & ~(size_t)255));
-    if (!dd) return set_error(ctx, SVO_ERR_HIP, "desc staging");
+    uint16_t* cs;
+    PyrDesc* dd;
+    if (!carve_scratch(ctx, kScratchFast, [&](Carver& c) {
+            cs = c.take<uint16_t>(npx);
+            dd = c.take<PyrDesc>(1);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    if (!stage_desc(ctx, img, dd)) return set_error(ctx, SVO_ERR_HIP, "desc staging");
     FastBatch b{dd, cs, nullptr, nullptr, nullptr, nullptr, npx, 0};
     SVO_HIP(ctx, launch_fast_score(b, 1, L.w, L.h, threshold, 1, ctx->stream));
     std::vector<uint16_t> h(npx);
@@ -374,17 +385,21 @@ int svo_fast_detect(svo_ctx* ctx, const svo_image* img, int threshold, int nonma
     const size_t npx = (size_t)L.w * L.h;
     const int nseg = (L.w + 63) / 64;
     const int kcap = cap > 0 ? cap : 1;
-    const size_t bbytes = sizeof(unsigned long long) * (size_t)L.h * nseg;
-    char* d = (char*)scratch(ctx, 0, bbytes + sizeof(int) * 2 * ((size_t)L.h + 64) + 1024);
-    uint8_t* dmask = mask ? (uint8_t*)scratch(ctx, 2, npx) : nullptr;
-    svo_keypoint* dout = (svo_keypoint*)scratch(ctx, 3, sizeof(svo_keypoint) * (size_t)kcap + 64);
-    if (!d || (mask && !dmask) || !dout) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    int* dn = (int*)((char*)dout + sizeof(svo_keypoint) * (size_t)kcap);
-    PyrDesc* dd = stage_desc(ctx, img, d);
-    if (!dd) return set_error(ctx, SVO_ERR_HIP, "desc staging");
-    unsigned long long* bits = (unsigned long long*)(d + 256);
-    int* rowcnt = (int*)((char*)bits + ((bbytes + 255) & ~(size_t)255));
-    int* rowoff = rowcnt + L.h + 64;
+    PyrDesc* dd;
+    unsigned long long* bits;
+    int *rowcnt, *rowoff;
+    const bool ok = carve_scratch(ctx, kScratchFast, [&](Carver& c) {
+        dd = c.take<PyrDesc>(1);
+        bits = c.take<unsigned long long>((size_t)L.h * nseg);
+        rowcnt = c.take<int>((size_t)L.h + 64);
+        rowoff = c.take<int>((size_t)L.h + 64);
+    });
+    uint8_t* dmask = mask ? (uint8_t*)scratch(ctx, kScratchMask, npx) : nullptr;
+    // one member: kcap keypoints, then their count at the head of one more
+    svo_keypoint* dout = (svo_keypoint*)scratch(ctx, kScratchFastOut, sizeof(svo_keypoint) * ((size_t)kcap + 1));
+    if (!ok || (mask && !dmask) || !dout) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    int* dn = (int*)(dout + kcap);
+    if (!stage_desc(ctx, img, dd)) return set_error(ctx, SVO_ERR_HIP, "desc staging");
     if (mask) SVO_HIP(ctx, hipMemcpyAsync(dmask, mask, npx, hipMemcpyHostToDevice, ctx->stream));
     FastDetBatch b{dd, dmask, bits, rowcnt, rowoff, dout, dn, npx, nseg, cap};
     b.padded = true;  // an svo_image level
@@ -403,8 +418,8 @@ int svo_mask_boxes(svo_ctx* ctx, int w, int h, const float* pts_xy, int n, float
     if (!ctx || w <= 0 || h <= 0 || !mask || n < 0 || (n > 0 && !pts_xy))
         return set_error(ctx, SVO_ERR_ARG, "svo_mask_boxes: bad arguments");
     size_t npx = (size_t)w * h;
-    uint8_t* dmask = (uint8_t*)scratch(ctx, 2, npx);
-    float* dpts = (float*)scratch(ctx, 4, sizeof(float) * 2 * (size_t)(n > 0 ? n : 1));
+    uint8_t* dmask = (uint8_t*)scratch(ctx, kScratchMask, npx);
+    float* dpts = (float*)scratch(ctx, kScratchMaskPts, sizeof(float) * 2 * (size_t)(n > 0 ? n : 1));
     if (!dmask || !dpts) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     if (n > 0) SVO_HIP(ctx, hipMemcpyAsync(dpts, pts_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, launch_mask_boxes(w, h, dpts, nullptr, n, n, 1, half, dmask, ctx->stream));
@@ -424,15 +439,18 @@ int svo_bucket_features(svo_ctx* ctx, const float* xy, const int* ages, int n, i
     if (nw <= 0) return set_error(ctx, SVO_ERR_ARG, "svo_bucket_features: bucket wider than image");
     (void)nh;
     size_t scr_ints = bucket_scratch_ints(img_w, img_h, bucket_size, per_bucket, n);
-    int* scr = (int*)scratch(ctx, 5, sizeof(int) * scr_ints);
-    int ncap = cap > 0 ? cap : 1;
-    char* io = (char*)scratch(ctx, 6, sizeof(float) * 2 * ((size_t)n + ncap) + sizeof(int) * ((size_t)n + ncap) + 256);
-    if (!scr || !io) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    float* dxy = (float*)io;
-    int* dages = (int*)(dxy + 2 * (size_t)n);
-    float* dxy_out = (float*)(dages + n);
-    int* dages_out = (int*)(dxy_out + 2 * (size_t)ncap);
-    int* dn = dages_out + ncap;
+    int* scr = (int*)scratch(ctx, kScratchSolve, sizeof(int) * scr_ints);
+    const size_t ncap = cap > 0 ? cap : 1;
+    float *dxy, *dxy_out;
+    int *dages, *dages_out, *dn;
+    if (!carve_scratch(ctx, kScratchPoints, [&](Carver& c) {
+            dxy = c.take<float>(2 * (size_t)n);
+            dages = c.take<int>(n);
+            dxy_out = c.take<float>(2 * ncap);
+            dages_out = c.take<int>(ncap);
+            dn = c.take<int>(1);
+        }) || !scr)
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     if (n > 0) {
         SVO_HIP(ctx, hipMemcpyAsync(dxy, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
         if (ages) SVO_HIP(ctx, hipMemcpyAsync(dages, ages, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -490,25 +508,28 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
     size_t doff[kMaxLevels];
     int dpitch[kMaxLevels];
     const size_t dbytes = deriv_layout(prev->w, prev->h, ml + 1, doff, dpitch);
-    size_t bytes = (size_t)n * (8 + 8 + 1 + 4 + 4) + 2 * sizeof(PyrDesc) + sizeof(DerivDesc) + dbytes + 2048;
-    char* d = (char*)scratch(ctx, 7, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    PyrDesc* ddesc = (PyrDesc*)d;
-    DerivDesc* dder = (DerivDesc*)(d + 2 * sizeof(PyrDesc));
-    char* dbase = (char*)(((uintptr_t)(d + 2 * sizeof(PyrDesc) + sizeof(DerivDesc)) + 255) & ~(uintptr_t)255);
-    d = dbase + ((dbytes + 255) & ~(size_t)255);
-    float* dprev = (float*)d;
-    float* dnext = dprev + 2 * (size_t)n;
-    float* derr = dnext + 2 * (size_t)n;
-    int* diters = (int*)(derr + n);
-    uint8_t* dst = (uint8_t*)(diters + n);
-    SVO_HIP(ctx, hipMemcpyAsync(dprev, prev_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
-    if (flags & SVO_LK_USE_INITIAL_FLOW)
-        SVO_HIP(ctx, hipMemcpyAsync(dnext, next_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
-    struct Staged {
+    struct Staged {  // one upload
         PyrDesc pd[2];
         DerivDesc dd;
     };
+    Staged* ds;
+    char* dbase;
+    float *dprev, *dnext, *derr;
+    int* diters;
+    uint8_t* dst;
+    if (!carve_scratch(ctx, kScratchTrack, [&](Carver& c) {
+            ds = c.take<Staged>(1);
+            dbase = c.take<char>(dbytes);
+            dprev = c.take<float>(2 * (size_t)n);
+            dnext = c.take<float>(2 * (size_t)n);
+            derr = c.take<float>(n);
+            diters = c.take<int>(n);
+            dst = c.take<uint8_t>(n);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    SVO_HIP(ctx, hipMemcpyAsync(dprev, prev_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (flags & SVO_LK_USE_INITIAL_FLOW)
+        SVO_HIP(ctx, hipMemcpyAsync(dnext, next_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
     Staged* hs = (Staged*)pinned(ctx, sizeof(Staged));
     if (!hs) return set_error(ctx, SVO_ERR_HIP, "pinned alloc");
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pinned staging is reused
@@ -518,10 +539,10 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
         hs->dd.data[l] = l <= ml ? (uint32_t*)(dbase + doff[l]) : nullptr;
         hs->dd.pitch[l] = l <= ml ? dpitch[l] : 0;
     }
-    SVO_HIP(ctx, hipMemcpyAsync(ddesc, hs, sizeof(Staged), hipMemcpyHostToDevice, ctx->stream));
+    SVO_HIP(ctx, hipMemcpyAsync(ds, hs, sizeof(Staged), hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemsetAsync(dbase, 0, dbytes, ctx->stream));  // the zero borders
-    SVO_HIP(ctx, launch_scharr(ddesc, dder, 1, prev->w, prev->h, ml + 1, ctx->stream));
-    LKBatch b{ddesc, ddesc + 1, dder, dprev, dnext, dst, err ? derr : nullptr, diters, nullptr, n, n};
+    SVO_HIP(ctx, launch_scharr(ds->pd, &ds->dd, 1, prev->w, prev->h, ml + 1, ctx->stream));
+    LKBatch b{ds->pd, ds->pd + 1, &ds->dd, dprev, dnext, dst, err ? derr : nullptr, diters, nullptr, n, n};
     SVO_HIP(ctx, launch_lk(b, 1, n, p, ctx->stream));
     std::vector<int> it(n);
     SVO_HIP(ctx, hipMemcpyAsync(next_xy, dnext, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -554,20 +575,24 @@ static int rows_match(svo_ctx* ctx, const char* who, const svo_image* left, cons
     if (n == 0) return SVO_OK;
     const bool guided = d_prior && guide > 0;
     const size_t N = (size_t)n;
-    char* d = (char*)scratch(ctx, 7, 512 + N * (8 + 8 + 4 + 4 + 4 + 1));
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    static_assert(sizeof(PyrDesc) <= 256, "descriptor slot");
-    float* dpts = (float*)(d + 512);
-    float* dnext = dpts + 2 * N;
-    int* ddisp = (int*)(dnext + 2 * N);
-    int* dcost = ddisp + N;
-    int* dprior = dcost + N;
-    uint8_t* dst = (uint8_t*)(dprior + N);
-    const PyrDesc* dl = stage_desc(ctx, left, d);
-    const PyrDesc* dr = dl ? stage_desc(ctx, right, d + 256) : nullptr;
-    if (!dl || !dr) return set_error(ctx, SVO_ERR_HIP, "desc staging");
+    PyrDesc* dlr;  // left, right
+    float *dpts, *dnext;
+    int *ddisp, *dcost, *dprior;
+    uint8_t* dst;
+    if (!carve_scratch(ctx, kScratchTrack, [&](Carver& c) {
+            dlr = c.take<PyrDesc>(2);
+            dpts = c.take<float>(2 * N);
+            dnext = c.take<float>(2 * N);
+            ddisp = c.take<int>(N);
+            dcost = c.take<int>(N);
+            dprior = c.take<int>(N);
+            dst = c.take<uint8_t>(N);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    if (!stage_desc(ctx, left, dlr) || !stage_desc(ctx, right, dlr + 1))
+        return set_error(ctx, SVO_ERR_HIP, "desc staging");
     SVO_HIP(ctx, hipMemcpyAsync(dpts, pts_xy, sizeof(float) * 2 * N, hipMemcpyHostToDevice, ctx->stream));
-    StereoRowsBatch b{dl, dr, dpts, dnext, dst, disparity ? ddisp : nullptr, cost ? dcost : nullptr, nullptr, n, n};
+    StereoRowsBatch b{dlr, dlr + 1, dpts, dnext, dst, disparity ? ddisp : nullptr, cost ? dcost : nullptr, nullptr, n, n};
     if (guided) {
         SVO_HIP(ctx, hipMemcpyAsync(dprior, d_prior, sizeof(int) * N, hipMemcpyHostToDevice, ctx->stream));
         SVO_HIP(ctx, launch_stereo_rows_guided(b, 1, n, *params, dprior, guide, 0, ctx->stream));
@@ -603,13 +628,16 @@ int svo_stereo_row_priors(svo_ctx* ctx, const int* mid, int n, const int* prev_m
         return set_error(ctx, SVO_ERR_ARG, "svo_stereo_row_priors: bad arguments");
     if (n == 0) return SVO_OK;
     const size_t N = (size_t)n, M = (size_t)prev_n;
-    char* d = (char*)scratch(ctx, 7, 256 + N * 8 + M * 16);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    int* dmid = (int*)d;
-    int* dout = dmid + N;
-    int* dpm = dout + N;
-    float* dpxy = (float*)(dpm + M);
-    float* dpur = dpxy + 2 * M;
+    int *dmid, *dout, *dpm;
+    float *dpxy, *dpur;
+    if (!carve_scratch(ctx, kScratchTrack, [&](Carver& c) {
+            dmid = c.take<int>(N);
+            dout = c.take<int>(N);
+            dpm = c.take<int>(M);
+            dpxy = c.take<float>(2 * M);
+            dpur = c.take<float>(M);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     SVO_HIP(ctx, hipMemcpyAsync(dmid, mid, sizeof(int) * N, hipMemcpyHostToDevice, ctx->stream));
     if (M) {
         SVO_HIP(ctx, hipMemcpyAsync(dpm, prev_mid, sizeof(int) * M, hipMemcpyHostToDevice, ctx->stream));
@@ -642,17 +670,19 @@ int svo_pnp_residuals(svo_ctx* ctx, const float* obj_xyz, const float* img_xy, i
         return SVO_OK;
     }
     const int words = (n + 31) / 32;
-    size_t bytes = sizeof(float) * 5 * (size_t)n + sizeof(double) * 12 * (size_t)m +
-                   (err ? sizeof(float) * (size_t)n * m : 0) + sizeof(uint32_t) * (size_t)words * m +
-                   sizeof(int) * (size_t)m + 1024;
-    char* d = (char*)scratch(ctx, 7, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    double* dh = (double*)d;
-    float* dobj = (float*)(dh + 12 * (size_t)m);
-    float* dimg = dobj + 3 * (size_t)n;
-    int* dcnt = (int*)(dimg + 2 * (size_t)n);
-    uint32_t* dbits = (uint32_t*)(dcnt + m);
-    float* derr = err ? (float*)(dbits + (size_t)words * m) : nullptr;
+    double* dh;
+    float *dobj, *dimg, *derr;
+    int* dcnt;
+    uint32_t* dbits;
+    if (!carve_scratch(ctx, kScratchTrack, [&](Carver& c) {
+            dh = c.take<double>(12 * (size_t)m);
+            dobj = c.take<float>(3 * (size_t)n);
+            dimg = c.take<float>(2 * (size_t)n);
+            dcnt = c.take<int>(m);
+            dbits = c.take<uint32_t>((size_t)words * m);
+            derr = err ? c.take<float>((size_t)n * m) : nullptr;
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     SVO_HIP(ctx, hipMemcpyAsync(dh, hyp_Rt, sizeof(double) * 12 * m, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dobj, obj_xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dimg, img_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
@@ -710,13 +740,16 @@ int svo_epnp_subsets(svo_ctx* ctx, const float* subsets, int m, const double K[9
         }
         return SVO_OK;
     }
-    const size_t bytes = sizeof(double) * (9 + 12 * (size_t)m) + sizeof(float) * 25 * (size_t)m + sizeof(int) * m + 1024;
-    char* d = (char*)scratch(ctx, 9, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    double* dK = (double*)d;
-    double* dRt = dK + 9;
-    float* dsub = (float*)(dRt + 12 * (size_t)m);
-    int* dok = (int*)(dsub + 25 * (size_t)m);
+    double *dK, *dRt;
+    float* dsub;
+    int* dok;
+    if (!carve_scratch(ctx, kScratchEpnp, [&](Carver& c) {
+            dK = c.take<double>(9);
+            dRt = c.take<double>(12 * (size_t)m);
+            dsub = c.take<float>(25 * (size_t)m);
+            dok = c.take<int>(m);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     SVO_HIP(ctx, hipMemcpyAsync(dK, K, sizeof(double) * 9, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dsub, subsets, sizeof(float) * 25 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     // 1: a wave per subset (the QL variant); 6: a lane per subset (the front end's solver)
@@ -733,14 +766,15 @@ int svo_triangulate_points(svo_ctx* ctx, const float P1[12], const float P2[12],
     if (!ctx || !P1 || !P2 || n < 0 || (n > 0 && (!pts1 || !pts2)))
         return set_error(ctx, SVO_ERR_ARG, "svo_triangulate_points: bad arguments");
     if (n == 0) return SVO_OK;
-    const size_t bytes = sizeof(float) * (24 + 4 * (size_t)n + 7 * (size_t)n) + 1024;
-    float* d = (float*)scratch(ctx, 6, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    float* dP = d;
-    float* dp1 = dP + 24;
-    float* dp2 = dp1 + 2 * (size_t)n;
-    float* dh = dp2 + 2 * (size_t)n;
-    float* dx = dh + 4 * (size_t)n;
+    float *dP, *dp1, *dp2, *dh, *dx;
+    if (!carve_scratch(ctx, kScratchPoints, [&](Carver& c) {
+            dP = c.take<float>(24);  // P1, P2
+            dp1 = c.take<float>(2 * (size_t)n);
+            dp2 = c.take<float>(2 * (size_t)n);
+            dh = c.take<float>(4 * (size_t)n);
+            dx = c.take<float>(3 * (size_t)n);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     SVO_HIP(ctx, hipMemcpyAsync(dP, P1, sizeof(float) * 12, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dP + 12, P2, sizeof(float) * 12, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dp1, pts1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 
+#include "layout.hpp"
 #include "svo_gpu.h"
 
 namespace svo {
@@ -54,6 +55,33 @@ struct RectMapsDev {
     int raw_w, raw_h, w, h;
 };
 
+// The owners of a context's scratch buffers. A slot is shared only among the
+// entry points its comment names: each of them enqueues on ctx->stream alone and
+// synchronises that stream before it returns, so a buffer's previous user is
+// done before the next one writes it.
+enum ScratchSlot {
+    kScratchFast,       // svo_fast_score_map, svo_fast_detect: the detector's workspace
+    kScratchDescribe,   // orb_describe.cpp: the descriptor entries' blur_levels, svo_match_hamming(_time)
+    kScratchMask,       // svo_fast_detect, svo_mask_boxes: the mask
+    kScratchFastOut,    // svo_fast_detect: keypoints and their count
+    kScratchMaskPts,    // svo_mask_boxes: the box centres
+    kScratchSolve,      // svo_bucket_features, svo_solve_pnp_ransac, refine.cpp's entries
+    kScratchPoints,     // svo_bucket_features (points in and out), svo_triangulate_points
+    kScratchTrack,      // svo_calc_optical_flow_pyr_lk, svo_stereo_match_rows(_guided),
+                        // svo_stereo_row_priors, svo_pnp_residuals
+    kScratchIngest0,    // ingest_bgr alone, which returns with its H2D and kernel in flight:
+    kScratchIngest1,    //   the device ends of its pinned double buffer
+    kScratchScharr,     // svo_image_scharr_level
+    kScratchEpnp,       // svo_epnp_subsets
+    kScratchBaLists,    // bundle.cpp's upload_lists (svo_ba_stage_lists(_stereo), svo_ba_time_staging)
+    kScratchOrb,        // orb_build_levels: every ORB entry of orb_detect.cpp and orb_describe.cpp
+    kScratchBa,         // bundle.cpp's alloc_staged: the LM's block of every bundle adjustment entry
+    kScratchBaStage,    // bundle.cpp's stage_work: the staging chain of the entries that stage lists
+    kScratchRectify,    // svo_image_upload_raw, svo_remap: the raw frame (the one slot whose users
+                        // synchronise as they enter: upload_raw returns with its kernel in flight)
+    kScratchRefine,     // refine_device.cpp's entries, svo_frontend_refine_poses
+    kScratchSlots       // the count
+};
 }  // namespace svo
 
 struct svo_rect_maps {
@@ -80,7 +108,7 @@ struct svo_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     int64_t lk_iters = 0;
-    svo_scratch s[15];
+    svo_scratch s[svo::kScratchSlots];
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // colour ingest: pinned double buffer (host copy of frame k+1 overlaps the
@@ -102,8 +130,16 @@ namespace svo {
 
 int set_error(svo_ctx* ctx, int code, const char* fmt, ...);
 // Grow scratch slot `slot` to >= bytes; returns device pointer or nullptr.
-void* scratch(svo_ctx* ctx, int slot, size_t bytes);
+void* scratch(svo_ctx* ctx, ScratchSlot slot, size_t bytes);
 void* pinned(svo_ctx* ctx, size_t bytes);
+// The block `layout` describes, in scratch slot `slot`: measured, grown to, placed.
+// False: the allocation failed.
+template <class F>
+bool carve_scratch(svo_ctx* ctx, ScratchSlot slot, F&& layout) {
+    void* d = scratch(ctx, slot, layout_bytes(layout));
+    if (d) layout_place(d, layout);
+    return d != nullptr;
+}
 
 // Kernel launchers (implemented in the .hip files).
 hipError_t launch_pyramid(const svo_image* img, int first_level, hipStream_t st);

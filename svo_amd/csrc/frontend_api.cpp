@@ -168,30 +168,26 @@ static int fe_window_enable(svo_frontend* fe, int window, bool stereo) {
     if (stereo && !(std::isfinite(fe_baseline(fe)) && fe_baseline(fe) > 0))
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_window_enable_stereo: P_right gives no baseline > 0");
     const size_t S = fe->S, Wn = window, CAP = fe->CAP;
-    size_t bytes = 0;
-    char* const base0 = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1 && hipMalloc(&w.mem, bytes) != hipSuccess) {
-            w.mem = nullptr;
-            w.ring = WindowRing{};  // (the sizing pass left offsets in it)
-            w.ur_feat = nullptr;
-            return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: hipMalloc(%zu)", bytes);
-        }
-        char* p = pass == 0 ? base0 : (char*)w.mem;
-        w.ring.window = window;
-        w.ring.cap = fe->CAP;
-        w.ring.n = carve<int>(p, S * Wn);
-        w.ring.epoch = carve<int>(p, S * Wn);
-        w.ring.xy = carve<float>(p, 2 * S * Wn * CAP);
-        w.ring.mid = carve<int>(p, S * Wn * CAP);
-        w.ring.map_epoch = carve<int>(p, S);
-        w.sel_slot = carve<int>(p, S * Wn);
-        w.sel_cnt = carve<int>(p, S * Wn);
-        w.sel_nc = carve<int>(p, S);
-        w.ring.ur = stereo ? carve<float>(p, S * Wn * CAP) : nullptr;
-        w.ur_feat = stereo ? carve<float>(p, S * CAP) : nullptr;
-        bytes = (size_t)(p - (pass == 0 ? base0 : (char*)w.mem)) + 256;
+    auto layout = [&](Carver& p) {
+        w.ring.n = p.take<int>(S * Wn);
+        w.ring.epoch = p.take<int>(S * Wn);
+        w.ring.xy = p.take<float>(2 * S * Wn * CAP);
+        w.ring.mid = p.take<int>(S * Wn * CAP);
+        w.ring.map_epoch = p.take<int>(S);
+        w.sel_slot = p.take<int>(S * Wn);
+        w.sel_cnt = p.take<int>(S * Wn);
+        w.sel_nc = p.take<int>(S);
+        w.ring.ur = stereo ? p.take<float>(S * Wn * CAP) : nullptr;
+        w.ur_feat = stereo ? p.take<float>(S * CAP) : nullptr;
+    };
+    const size_t bytes = layout_bytes(layout);  // (leaves every pointer null)
+    if (hipMalloc(&w.mem, bytes) != hipSuccess) {
+        w.mem = nullptr;
+        return set_error(ctx, SVO_ERR_HIP, "svo_frontend_window_enable: hipMalloc(%zu)", bytes);
     }
+    layout_place(w.mem, layout);
+    w.ring.window = window;
+    w.ring.cap = fe->CAP;
     if (hipHostMalloc((void**)&w.h_pose, sizeof(double) * 12 * S * Wn, hipHostMallocCoherent | hipHostMallocMapped) !=
         hipSuccess) {
         (void)hipFree(w.mem);
@@ -337,7 +333,7 @@ int svo_frontend_refine_poses(svo_frontend* fe, double huber_delta, int max_iter
     SVO_HIP(ctx, launch_window_select(w.ring, fe_window_order(fe), fe->S, w.sel_slot, w.sel_cnt, w.sel_nc, st));
     // the results: [S][2] costs, [S] iterations, [S] counts, one block and one download
     const size_t S = (size_t)fe->S, bytes = S * (2 * sizeof(double) + 2 * sizeof(int));
-    char* d = (char*)scratch(ctx, 14, bytes);
+    char* d = (char*)scratch(ctx, kScratchRefine, bytes);
     if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     PoseRefineBatch b;
     b.P = fe->S;

@@ -112,58 +112,55 @@ int create_frames(svo_frontend* fe) {
     return SVO_OK;
 }
 
-// device state: one allocation, laid out by the carve sequence below (run once
-// on a null base to size it)
+// device state: one allocation, laid out by the sequence below
 int create_device_state(svo_frontend* fe) {
     svo_ctx* ctx = fe->ctx;
     const svo_frontend_config& c = fe->cfg;
     const int S = fe->S, CAP = fe->CAP;
-    size_t bytes = 0;
-    char* const dbase0 = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1 && hipMalloc(&fe->dmem, bytes) != hipSuccess)
-            return set_error(ctx, SVO_ERR_HIP, "svo_frontend_create: hipMalloc(%zu)", bytes);
-        char* p = pass == 0 ? dbase0 : (char*)fe->dmem;
-        fe->d_desc = carve<PyrDesc>(p, (size_t)fe->T * S);
-        fe->d_desc_r = carve<PyrDesc>(p, (size_t)fe->T * S);
-        fe->xyA = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->next_xy = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->st_xy = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->st_next = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->st_status = carve<uint8_t>(p, (size_t)S * CAP);
-        fe->st_X = carve<float4>(p, (size_t)S * CAP);
-        fe->st_n = carve<int>(p, S);
-        fe->pend0 = carve<int>(p, S);
-        fe->pend_n = carve<int>(p, S);
-        fe->spec_n = carve<int>(p, S);
-        fe->kps = carve<float>(p, 3 * (size_t)S * fe->KCAP);
-        fe->cand = carve<float>(p, 2 * (size_t)S * fe->BCAP);
-        fe->midA = carve<int>(p, (size_t)S * CAP);
-        fe->midB = carve<int>(p, (size_t)S * CAP);
-        fe->iters = carve<int>(p, (size_t)S * CAP);
-        fe->nA = carve<int>(p, S);
-        fe->kn = carve<int>(p, S);
-        fe->bn = carve<int>(p, S);
-        fe->map_n = carve<int>(p, S);
-        fe->added = carve<int>(p, S);
-        fe->rowcnt = carve<int>(p, (size_t)S * c.height);
-        fe->scr = carve<int>(p, fe->bscr * S);
-        fe->status = carve<uint8_t>(p, (size_t)S * CAP);
-        fe->fbits = carve<unsigned long long>(p, (size_t)S * c.height * ((c.width + 63) / 64));
-        fe->rowoff = carve<int>(p, (size_t)S * c.height);
-        fe->map = carve<double>(p, 3 * (size_t)S * fe->MAPCAP);
-        fe->box_binned = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->box_band = carve<int>(p, (size_t)S * fast_box_cells(c.width, c.height));
+    auto layout = [&](Carver& p) {
+        fe->d_desc = p.take<PyrDesc>((size_t)fe->T * S);
+        fe->d_desc_r = p.take<PyrDesc>((size_t)fe->T * S);
+        fe->xyA = p.take<float>(2 * (size_t)S * CAP);
+        fe->next_xy = p.take<float>(2 * (size_t)S * CAP);
+        fe->st_xy = p.take<float>(2 * (size_t)S * CAP);
+        fe->st_next = p.take<float>(2 * (size_t)S * CAP);
+        fe->st_status = p.take<uint8_t>((size_t)S * CAP);
+        fe->st_X = p.take<float4>((size_t)S * CAP);
+        fe->st_n = p.take<int>(S);
+        fe->pend0 = p.take<int>(S);
+        fe->pend_n = p.take<int>(S);
+        fe->spec_n = p.take<int>(S);
+        fe->kps = p.take<float>(3 * (size_t)S * fe->KCAP);
+        fe->cand = p.take<float>(2 * (size_t)S * fe->BCAP);
+        fe->midA = p.take<int>((size_t)S * CAP);
+        fe->midB = p.take<int>((size_t)S * CAP);
+        fe->iters = p.take<int>((size_t)S * CAP);
+        fe->nA = p.take<int>(S);
+        fe->kn = p.take<int>(S);
+        fe->bn = p.take<int>(S);
+        fe->map_n = p.take<int>(S);
+        fe->added = p.take<int>(S);
+        fe->rowcnt = p.take<int>((size_t)S * c.height);
+        fe->scr = p.take<int>(fe->bscr * S);
+        fe->status = p.take<uint8_t>((size_t)S * CAP);
+        fe->fbits = p.take<unsigned long long>((size_t)S * c.height * ((c.width + 63) / 64));
+        fe->rowoff = p.take<int>((size_t)S * c.height);
+        fe->map = p.take<double>(3 * (size_t)S * fe->MAPCAP);
+        fe->box_binned = p.take<float>(2 * (size_t)S * CAP);
+        fe->box_band = p.take<int>((size_t)S * fast_box_cells(c.width, c.height));
         for (int k = 0; k < 2; k++) {
-            fe->xyB_b[k] = carve<float>(p, 2 * (size_t)S * CAP);
-            fe->obj_b[k] = carve<float>(p, 3 * (size_t)S * CAP);
-            fe->nB_b[k] = carve<int>(p, S);
+            fe->xyB_b[k] = p.take<float>(2 * (size_t)S * CAP);
+            fe->obj_b[k] = p.take<float>(3 * (size_t)S * CAP);
+            fe->nB_b[k] = p.take<int>(S);
         }
         fe->xyB = fe->xyB_b[0];
         fe->obj = fe->obj_b[0];
         fe->nB = fe->nB_b[0];
-        bytes = (size_t)(p - (pass == 0 ? dbase0 : (char*)fe->dmem)) + 256;
-    }
+    };
+    const size_t bytes = layout_bytes(layout);
+    if (hipMalloc(&fe->dmem, bytes) != hipSuccess)
+        return set_error(ctx, SVO_ERR_HIP, "svo_frontend_create: hipMalloc(%zu)", bytes);
+    layout_place(fe->dmem, layout);
     (void)hipMemsetAsync(fe->dmem, 0, bytes, ctx->stream);
     return SVO_OK;
 }
@@ -171,15 +168,15 @@ int create_device_state(svo_frontend* fe) {
 // host mirrors (pinned): both parities of the full point copies
 int create_pinned_mirrors(svo_frontend* fe) {
     const int S = fe->S, CAP = fe->CAP;
-    const size_t hb = 2 * (((sizeof(float) * 2 * (size_t)S * CAP + 255) & ~(size_t)255) +
-                           ((sizeof(float) * 3 * (size_t)S * CAP + 255) & ~(size_t)255)) + 4096;
-    if (hipHostMalloc(&fe->hmem, hb, hipHostMallocDefault) != hipSuccess)
+    auto layout = [&](Carver& p) {
+        for (int k = 0; k < 2; k++) {
+            fe->h_xyB_b[k] = p.take<float>(2 * (size_t)S * CAP);
+            fe->h_obj_b[k] = p.take<float>(3 * (size_t)S * CAP);
+        }
+    };
+    if (hipHostMalloc(&fe->hmem, layout_bytes(layout), hipHostMallocDefault) != hipSuccess)
         return set_error(fe->ctx, SVO_ERR_HIP, "svo_frontend_create: hipHostMalloc");
-    char* p = (char*)fe->hmem;
-    for (int k = 0; k < 2; k++) {
-        fe->h_xyB_b[k] = carve<float>(p, 2 * (size_t)S * CAP);
-        fe->h_obj_b[k] = carve<float>(p, 3 * (size_t)S * CAP);
-    }
+    layout_place(fe->hmem, layout);
     fe->h_xyB = fe->h_xyB_b[0];
     fe->h_obj = fe->h_obj_b[0];
     return SVO_OK;
@@ -191,55 +188,45 @@ int create_coherent(svo_frontend* fe) {
     // zero-copy scoring buffers (coherent: the kernel's writes are visible to the
     // host once the stream is synchronised)
     {
-        const size_t zb = ((sizeof(double) * 12 * (size_t)S * kRansacChunk + 255) & ~(size_t)255) +
-                          ((sizeof(uint32_t) * (size_t)S * kRansacChunk * fe->WORDS + 255) & ~(size_t)255) +
-                          sizeof(int) * (size_t)S * kRansacChunk + 256;
-        if (hipHostMalloc(&fe->zmem, zb, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+        auto layout = [&](Carver& p) {
+            fe->z_hyps = p.take<double>(12 * (size_t)S * kRansacChunk);
+            fe->z_bits = p.take<uint32_t>((size_t)S * kRansacChunk * fe->WORDS);
+            fe->z_cnt = p.take<int>((size_t)S * kRansacChunk);
+        };
+        if (hipHostMalloc(&fe->zmem, layout_bytes(layout), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
             fe->zmem = nullptr;
             return set_error(ctx, SVO_ERR_HIP, "svo_frontend_create: host-coherent scoring buffers");
         }
-        char* p = (char*)fe->zmem;
-        fe->z_hyps = carve<double>(p, 12 * (size_t)S * kRansacChunk);
-        fe->z_bits = carve<uint32_t>(p, (size_t)S * kRansacChunk * fe->WORDS);
-        fe->z_cnt = carve<int>(p, (size_t)S * kRansacChunk);
+        layout_place(fe->zmem, layout);
     }
     // host-coherent outputs the kernels write directly (no D2H copies on the
     // critical path): post-LK counts / iteration sums / RANSAC subsets, the
     // keyframe's counts; the inlier bits the tail and the statistics read (parity
     // pair); the keyframe targets the keyframe kernels read
     {
-        size_t zb = 0;
-        auto add = [&](size_t b) { zb = ((zb + 255) & ~(size_t)255) + b; };
-        for (int k = 0; k < 5; k++) add(sizeof(int) * S);  // h_nB, h_nA, h_added, h_target, h_over
-        add(sizeof(long long) * S);
-        add(sizeof(float) * kSampleFloats * kRansacPrefetch * (size_t)S);
-        add(sizeof(uint32_t) * (size_t)S * fe->WORDS);
-        add(sizeof(uint32_t) * (size_t)S * fe->WORDS);
-        add(sizeof(double) * kSqpnpStats * (size_t)S);
-        add(sizeof(double) * 12 * (size_t)S);
-        add(sizeof(double) * 6 * (size_t)S);
-        add(sizeof(SqpnpFitIn) * (size_t)S);
-        add(1024);
+        auto layout = [&](Carver& p) {
+            fe->h_nB = p.take<int>(S);
+            fe->h_nA = p.take<int>(S);
+            fe->h_added = p.take<int>(S);
+            fe->h_target = p.take<int>(S);
+            fe->h_over = p.take<int>(S);
+            fe->h_itsum = p.take<long long>(S);
+            fe->h_samp = p.take<float>((size_t)kSampleFloats * kRansacPrefetch * S);
+            fe->h_best_b[0] = p.take<uint32_t>((size_t)S * fe->WORDS);
+            fe->h_best_b[1] = p.take<uint32_t>((size_t)S * fe->WORDS);
+            fe->h_stats = p.take<double>(kSqpnpStats * (size_t)S);
+            fe->h_pose = p.take<double>(12 * (size_t)S);
+            fe->h_pose6 = p.take<double>(6 * (size_t)S);
+            fe->h_fitin = p.take<SqpnpFitIn>((size_t)S);
+        };
+        const size_t zb = layout_bytes(layout);
         if (hipHostMalloc(&fe->zout, zb, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
             fe->zout = nullptr;
             return set_error(ctx, SVO_ERR_HIP, "svo_frontend_create: host-coherent alloc");
         }
         std::memset(fe->zout, 0, zb);
-        char* p = (char*)fe->zout;
-        fe->h_nB = carve<int>(p, S);
-        fe->h_nA = carve<int>(p, S);
-        fe->h_added = carve<int>(p, S);
-        fe->h_target = carve<int>(p, S);
-        fe->h_over = carve<int>(p, S);
-        fe->h_itsum = carve<long long>(p, S);
-        fe->h_samp = carve<float>(p, (size_t)kSampleFloats * kRansacPrefetch * S);
-        fe->h_best_b[0] = carve<uint32_t>(p, (size_t)S * fe->WORDS);
-        fe->h_best_b[1] = carve<uint32_t>(p, (size_t)S * fe->WORDS);
+        layout_place(fe->zout, layout);
         fe->h_best = fe->h_best_b[0];
-        fe->h_stats = carve<double>(p, kSqpnpStats * (size_t)S);
-        fe->h_pose = carve<double>(p, 12 * (size_t)S);
-        fe->h_pose6 = carve<double>(p, 6 * (size_t)S);
-        fe->h_fitin = carve<SqpnpFitIn>(p, (size_t)S);
         for (int s = 0; s < S; s++) fe_set_pose(fe, s, false, nullptr, nullptr);
     }
     return SVO_OK;
@@ -254,16 +241,20 @@ int create_deriv_pyramids(svo_frontend* fe) {
     size_t doff[kMaxLevels];
     int dpitch[kMaxLevels];
     const size_t dbytes = (deriv_layout(c.width, c.height, fe->nlev, doff, dpitch) + 255) & ~(size_t)255;
-    if (hipMalloc(&fe->dermem, dbytes * 3 * S + 256 + sizeof(DerivDesc) * 3 * S) != hipSuccess)
+    char* base;
+    auto layout = [&](Carver& p) {
+        fe->d_der = p.take<DerivDesc>(3 * (size_t)S);
+        base = p.take<char>(dbytes * 3 * S);
+    };
+    if (hipMalloc(&fe->dermem, layout_bytes(layout)) != hipSuccess)
         return set_error(ctx, SVO_ERR_HIP, "svo_frontend_create: deriv alloc");
+    layout_place(fe->dermem, layout);
     std::vector<DerivDesc> hd(3 * (size_t)S);
-    char* base = (char*)fe->dermem + ((sizeof(DerivDesc) * 3 * S + 255) & ~(size_t)255);
     for (int k = 0; k < 3 * S; k++)
         for (int l = 0; l < kMaxLevels; l++) {
             hd[k].data[l] = l < fe->nlev ? (uint32_t*)(base + dbytes * k + doff[l]) : nullptr;
             hd[k].pitch[l] = l < fe->nlev ? dpitch[l] : 0;
         }
-    fe->d_der = (DerivDesc*)fe->dermem;
     SVO_HIP(ctx, hipMemsetAsync(base, 0, dbytes * 3 * S, ctx->stream));  // zero borders, never rewritten
     SVO_HIP(ctx, hipMemcpyAsync(fe->d_der, hd.data(), sizeof(DerivDesc) * hd.size(), hipMemcpyHostToDevice,
                                 ctx->stream));
@@ -530,17 +521,15 @@ int svo_frontend_set_stereo_tracking(svo_frontend* fe, const svo_stereo_rows_par
         return set_error(ctx, SVO_ERR_ARG, "svo_frontend_set_stereo_tracking: parameters out of range "
                                            "(svo_stereo_match_rows', guide 0..15)");
     const size_t n = (size_t)fe->S * fe->CAP;
-    size_t bytes = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) SVO_HIP(ctx, hipMalloc(&fe->trk_mem, bytes));
-        char* p = pass == 0 ? nullptr : (char*)fe->trk_mem;
-        char* const p0 = p;
-        fe->trk_prior = carve<int>(p, n);
-        fe->trk_n = carve<int>(p, fe->S);
-        fe->trk_next = carve<float>(p, 2 * n);
-        fe->trk_status = carve<uint8_t>(p, n);
-        bytes = (size_t)(p - p0) + 256;
-    }
+    auto layout = [&](Carver& p) {
+        fe->trk_prior = p.take<int>(n);
+        fe->trk_n = p.take<int>(fe->S);
+        fe->trk_next = p.take<float>(2 * n);
+        fe->trk_status = p.take<uint8_t>(n);
+    };
+    const size_t bytes = layout_bytes(layout);
+    SVO_HIP(ctx, hipMalloc(&fe->trk_mem, bytes));
+    layout_place(fe->trk_mem, layout);
     SVO_HIP(ctx, hipMemsetAsync(fe->trk_mem, 0, bytes, ctx->stream));
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     fe->ev_trk.assign(fe->T, nullptr);

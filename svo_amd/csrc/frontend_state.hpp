@@ -284,14 +284,6 @@ struct FeTrace {
     }
 };
 
-template <class T>
-T* carve(char*& p, size_t count) {
-    p = (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    T* r = (T*)p;
-    p += sizeof(T) * count;
-    return r;
-}
-
 // Phase timing (frontend_api.cpp): event pairs from a ring, folded into the
 // totals once complete.
 void ph_fold(svo_frontend* fe, bool wait);

@@ -50,7 +50,7 @@ hipError_t orb_batch_detect(OrbBatch* ob, const ImgLevel* lv0, const float* box_
                             hipStream_t st, const std::function<void(int, const std::function<void(int)>&)>& par,
                             int* overflow);
 
-// svo_orb_detect's workspace (scratch slot 10) and the scale and mask pyramids built in it
+// svo_orb_detect's workspace (scratch slot kScratchOrb) and the scale and mask pyramids built in it
 struct OrbLevels {
     OrbGeometry g;
     size_t mask_off[kMaxLevels];

@@ -16,8 +16,6 @@ using namespace svo;
 
 namespace {
 
-constexpr int kDescScratch = 1;  // scratch slot of the descriptor and matcher workspaces
-
 // patch_size odd in [5, 31]
 bool patch_ok(int patch_size) { return patch_size >= 5 && patch_size <= 31 && (patch_size & 1); }
 
@@ -93,37 +91,31 @@ struct TimedLoop {
 
 struct DescWork {
     PyrDesc blurred;
-    char* base;
-    size_t o_kp, o_dir, o_angle, o_desc, o_pat;
+    OrbDescKp* kp;
+    OrbDirection* dir;
+    float* angle;
+    uint8_t* desc;
+    int8_t* pat;
 };
 
 // Lays out the workspace for n keypoints on the levels of o and queues the blur.
 int blur_levels(svo_ctx* ctx, const OrbLevels& o, int n, const char* who, DescWork& w) {
     const OrbGeometry& g = o.g;
-    size_t off = 0;
-    auto take = [&off](size_t b) {
-        const size_t at = off;
-        off = (off + b + 255) & ~(size_t)255;
-        return at;
-    };
-    size_t lo[kMaxLevels];
-    int bp[kMaxLevels];
-    for (int l = 0; l < g.nlev; l++) {
-        bp[l] = (g.lw[l] + 63) & ~63;
-        lo[l] = take((size_t)bp[l] * g.lh[l]);
-    }
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    w.o_kp = take(sizeof(OrbDescKp) * nn);
-    w.o_dir = take(sizeof(OrbDirection) * nn);
-    w.o_angle = take(sizeof(float) * nn);
-    w.o_desc = take((size_t)SVO_ORB_DESC_BYTES * nn);
-    w.o_pat = take(2 * kOrbPatternPoints);
-    w.base = (char*)scratch(ctx, kDescScratch, off);
-    if (!w.base) return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
     w.blurred = PyrDesc{};
     w.blurred.nlevels = g.nlev;
-    for (int l = 0; l < g.nlev; l++)
-        w.blurred.lv[l] = ImgLevel{(const uint8_t*)(w.base + lo[l]), g.lw[l], g.lh[l], bp[l]};
+    if (!carve_scratch(ctx, kScratchDescribe, [&](Carver& c) {
+            for (int l = 0; l < g.nlev; l++) {
+                const int bp = (g.lw[l] + 63) & ~63;
+                w.blurred.lv[l] = ImgLevel{c.take<uint8_t>((size_t)bp * g.lh[l]), g.lw[l], g.lh[l], bp};
+            }
+            w.kp = c.take<OrbDescKp>(nn);
+            w.dir = c.take<OrbDirection>(nn);
+            w.angle = c.take<float>(nn);
+            w.desc = c.take<uint8_t>((size_t)SVO_ORB_DESC_BYTES * nn);
+            w.pat = c.take<int8_t>(2 * kOrbPatternPoints);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
     SVO_HIP(ctx, launch_orb_blur(o.lev, w.blurred, ctx->stream));
     return SVO_OK;
 }
@@ -152,26 +144,22 @@ int describe_levels(svo_ctx* ctx, const svo_orb_params* prm, const OrbLevels& o,
     DescWork w;
     const int rc = blur_levels(ctx, o, n, who, w);
     if (rc != SVO_OK) return rc;
-    OrbDescKp* dkp = (OrbDescKp*)(w.base + w.o_kp);
-    OrbDirection* ddir = (OrbDirection*)(w.base + w.o_dir);
-    float* dang = (float*)(w.base + w.o_angle);
-    uint8_t* ddesc = (uint8_t*)(w.base + w.o_desc);
-    int8_t* dpat = (int8_t*)(w.base + w.o_pat);
-    SVO_HIP(ctx, hipMemcpyAsync(dkp, hk.data(), sizeof(OrbDescKp) * n, hipMemcpyHostToDevice, st));
-    SVO_HIP(ctx, hipMemcpyAsync(dpat, pat, 2 * kOrbPatternPoints, hipMemcpyHostToDevice, st));
-    SVO_HIP(ctx, launch_orb_angle(o.lev, dkp, n, hp, umax, ddir, dang, st));
-    SVO_HIP(ctx, launch_orb_brief(w.blurred, dkp, n, dpat, ddir, reach, ddesc, st));
+    SVO_HIP(ctx, hipMemcpyAsync(w.kp, hk.data(), sizeof(OrbDescKp) * n, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(w.pat, pat, 2 * kOrbPatternPoints, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, launch_orb_angle(o.lev, w.kp, n, hp, umax, w.dir, w.angle, st));
+    SVO_HIP(ctx, launch_orb_brief(w.blurred, w.kp, n, w.pat, w.dir, reach, w.desc, st));
     if (time_reps > 0) {  // svo_orb_describe_time: the three kernels again, each `reps` times between events
         TimedLoop tl(ctx, time_reps);
         SVO_HIP(ctx, tl.run(&time_ms[0], [&] { return launch_orb_blur(o.lev, w.blurred, st); }));
-        SVO_HIP(ctx, tl.run(&time_ms[1], [&] { return launch_orb_angle(o.lev, dkp, n, hp, umax, ddir, dang, st); }));
+        SVO_HIP(ctx, tl.run(&time_ms[1],
+                            [&] { return launch_orb_angle(o.lev, w.kp, n, hp, umax, w.dir, w.angle, st); }));
         SVO_HIP(ctx, tl.run(&time_ms[2],
-                            [&] { return launch_orb_brief(w.blurred, dkp, n, dpat, ddir, reach, ddesc, st); }));
+                            [&] { return launch_orb_brief(w.blurred, w.kp, n, w.pat, w.dir, reach, w.desc, st); }));
     }
     std::vector<uint8_t> hd((size_t)SVO_ORB_DESC_BYTES * n);
     std::vector<float> ha(n);
-    SVO_HIP(ctx, hipMemcpyAsync(hd.data(), ddesc, hd.size(), hipMemcpyDeviceToHost, st));
-    SVO_HIP(ctx, hipMemcpyAsync(ha.data(), dang, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(hd.data(), w.desc, hd.size(), hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(ha.data(), w.angle, sizeof(float) * n, hipMemcpyDeviceToHost, st));
     SVO_HIP(ctx, hipStreamSynchronize(st));  // also: hk and pat have left the host
     std::memcpy(desc, hd.data(), hd.size());
     std::memcpy(valid, hv.data(), n);
@@ -281,24 +269,23 @@ int match_run(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_
     const size_t P = (size_t)n_problems;
     const size_t qb = P * q_stride * SVO_ORB_DESC_BYTES, tb = P * t_stride * SVO_ORB_DESC_BYTES;
     const size_t ob = sizeof(int) * 2 * P * q_stride;
-    size_t off = 0;
-    auto take = [&off](size_t b) {
-        const size_t at = off;
-        off = (off + b + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_q = take(qb), o_t = take(tb), o_nq = take(sizeof(int) * P), o_nt = take(sizeof(int) * P),
-                 o_idx = take(ob), o_dist = take(ob);
-    char* d = (char*)scratch(ctx, kDescScratch, off);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
-    SVO_HIP(ctx, hipMemcpyAsync(d + o_q, q, qb, hipMemcpyHostToDevice, st));
-    if (tb) SVO_HIP(ctx, hipMemcpyAsync(d + o_t, t, tb, hipMemcpyHostToDevice, st));
-    SVO_HIP(ctx, hipMemcpyAsync(d + o_nq, nq, sizeof(int) * P, hipMemcpyHostToDevice, st));
-    SVO_HIP(ctx, hipMemcpyAsync(d + o_nt, nt, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    uint32_t *dq, *dt;
+    int *dnq, *dnt, *didx, *ddist;
+    if (!carve_scratch(ctx, kScratchDescribe, [&](Carver& c) {
+            dq = c.take<uint32_t>(qb / 4);
+            dt = c.take<uint32_t>(tb / 4);
+            dnq = c.take<int>(P);
+            dnt = c.take<int>(P);
+            didx = c.take<int>(2 * P * q_stride);
+            ddist = c.take<int>(2 * P * q_stride);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
+    SVO_HIP(ctx, hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, st));
+    if (tb) SVO_HIP(ctx, hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dnq, nq, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dnt, nt, sizeof(int) * P, hipMemcpyHostToDevice, st));
     auto launch = [&] {
-        return launch_hamming_knn2((const uint32_t*)(d + o_q), (const uint32_t*)(d + o_t), (const int*)(d + o_nq),
-                                   (const int*)(d + o_nt), q_stride, t_stride, n_problems, max_nq, (int*)(d + o_idx),
-                                   (int*)(d + o_dist), st);
+        return launch_hamming_knn2(dq, dt, dnq, dnt, q_stride, t_stride, n_problems, max_nq, didx, ddist, st);
     };
     SVO_HIP(ctx, launch());
     if (time_reps > 0) {
@@ -309,8 +296,8 @@ int match_run(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_
     }
     // only the rows of live queries reach the caller: the padding up to the stride stays as it was
     std::vector<int> hi(2 * P * q_stride), hd(2 * P * q_stride);
-    SVO_HIP(ctx, hipMemcpyAsync(hi.data(), d + o_idx, ob, hipMemcpyDeviceToHost, st));
-    SVO_HIP(ctx, hipMemcpyAsync(hd.data(), d + o_dist, ob, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(hi.data(), didx, ob, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(hd.data(), ddist, ob, hipMemcpyDeviceToHost, st));
     SVO_HIP(ctx, hipStreamSynchronize(st));
     for (size_t p = 0; p < P; p++) {
         const size_t at = 2 * p * q_stride;

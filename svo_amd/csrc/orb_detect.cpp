@@ -226,12 +226,6 @@ OrbBatch* orb_batch_create(int S, int W, int H, const svo_orb_params& p) {
         return nullptr;
     }
     const OrbGeometry& g = ob->g;
-    size_t off = 0;
-    auto take = [&off](size_t b) {
-        const size_t o = off;
-        off = (off + b + 255) & ~(size_t)255;
-        return o;
-    };
     size_t img_seq = 0;
     for (int l = 1; l < g.nlev; l++) {
         ob->img_off[l] = img_seq;
@@ -244,27 +238,23 @@ OrbBatch* orb_batch_create(int S, int W, int H, const svo_orb_params& p) {
         mask_bytes += ((size_t)S * g.lw[l] * g.lh[l] + 255) & ~(size_t)255;
     }
     const size_t LS = (size_t)g.nlev * S;
-    const size_t o_img = take(img_seq * S), o_mask = take(mask_bytes),
-                 o_bits = take(sizeof(unsigned long long) * S * (size_t)g.maxh * g.maxnseg),
-                 o_rc = take(sizeof(int) * S * (size_t)g.maxh), o_ro = take(sizeof(int) * S * (size_t)g.maxh),
-                 o_kp = take(sizeof(svo_keypoint) * LS * g.maxcap), o_resp = take(sizeof(float) * LS * g.maxcap),
-                 o_n = take(sizeof(int) * LS), o_tab = take(sizeof(uint32_t) * (g.tabs.size() + 1)),
-                 o_desc = take(sizeof(PyrDesc) * LS);
-    if (hipMalloc(&ob->mem, off) != hipSuccess) {
+    auto layout = [&](Carver& c) {
+        ob->img = c.take<uint8_t>(img_seq * S);
+        ob->mask = c.take<uint8_t>(mask_bytes);
+        ob->bits = c.take<unsigned long long>(S * (size_t)g.maxh * g.maxnseg);
+        ob->rowcnt = c.take<int>(S * (size_t)g.maxh);
+        ob->rowoff = c.take<int>(S * (size_t)g.maxh);
+        ob->kps = c.take<svo_keypoint>(LS * g.maxcap);
+        ob->resp = c.take<float>(LS * g.maxcap);
+        ob->n = c.take<int>(LS);
+        ob->tabs = c.take<uint32_t>(g.tabs.size() + 1);
+        ob->desc = c.take<PyrDesc>(LS);
+    };
+    if (hipMalloc(&ob->mem, layout_bytes(layout)) != hipSuccess) {
         delete ob;
         return nullptr;
     }
-    char* b = (char*)ob->mem;
-    ob->img = (uint8_t*)(b + o_img);
-    ob->mask = (uint8_t*)(b + o_mask);
-    ob->bits = (unsigned long long*)(b + o_bits);
-    ob->rowcnt = (int*)(b + o_rc);
-    ob->rowoff = (int*)(b + o_ro);
-    ob->kps = (svo_keypoint*)(b + o_kp);
-    ob->resp = (float*)(b + o_resp);
-    ob->n = (int*)(b + o_n);
-    ob->tabs = (uint32_t*)(b + o_tab);
-    ob->desc = (PyrDesc*)(b + o_desc);
+    layout_place(ob->mem, layout);
     if (!g.tabs.empty() &&
         hipMemcpy(ob->tabs, g.tabs.data(), sizeof(uint32_t) * g.tabs.size(), hipMemcpyHostToDevice) != hipSuccess) {
         orb_batch_destroy(ob);
@@ -417,28 +407,22 @@ int orb_build_levels(svo_ctx* ctx, const svo_image* img, const svo_orb_params* p
     // workspace: level images (level 0 is the caller's image), masks, FAST
     // scratch, keypoints [nlev][maxcap], Harris responses, coefficient tables
     const size_t tab_words = g.tabs.size();
-    const size_t bits_bytes = sizeof(unsigned long long) * (size_t)maxh * maxnseg;
-    size_t off = 0;
-    auto take = [&off](size_t b) {
-        size_t o = off;
-        off = (off + b + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_img = take(ibytes), o_mask = take(mbytes), o_bits = take(bits_bytes),
-                 o_rc = take(sizeof(int) * 2 * ((size_t)maxh + 64)),
-                 o_kp = take(sizeof(svo_keypoint) * (size_t)nlev * maxcap), o_n = take(sizeof(int) * kMaxLevels),
-                 o_resp = take(sizeof(float) * (size_t)nlev * maxcap), o_tab = take(sizeof(uint32_t) * tab_words),
-                 o_desc = take(sizeof(PyrDesc) * (kMaxLevels + 1));
-    char* ws = (char*)scratch(ctx, 10, off);
-    if (!ws) return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
-    uint8_t* dimg = (uint8_t*)(ws + o_img);
-    uint8_t* dmask = o.dmask = mask ? (uint8_t*)(ws + o_mask) : nullptr;
-    o.dkp = (svo_keypoint*)(ws + o_kp);
-    o.dn = (int*)(ws + o_n);
-    o.dresp = (float*)(ws + o_resp);
-    o.bits = (unsigned long long*)(ws + o_bits);
-    o.rowcnt = (int*)(ws + o_rc);
-    o.rowoff = o.rowcnt + maxh + 64;
+    uint8_t *dimg, *dmask;
+    uint32_t* dtab;
+    if (!carve_scratch(ctx, kScratchOrb, [&](Carver& c) {
+            dimg = c.take<uint8_t>(ibytes);
+            dmask = c.take<uint8_t>(mbytes);
+            o.bits = c.take<unsigned long long>((size_t)maxh * maxnseg);
+            o.rowcnt = c.take<int>((size_t)maxh + 64);
+            o.rowoff = c.take<int>((size_t)maxh + 64);
+            o.dkp = c.take<svo_keypoint>((size_t)nlev * maxcap);
+            o.dn = c.take<int>(kMaxLevels);
+            o.dresp = c.take<float>((size_t)nlev * maxcap);
+            dtab = c.take<uint32_t>(tab_words);
+            o.ddesc = c.take<PyrDesc>(kMaxLevels + 1);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
+    o.dmask = dmask = mask ? dmask : nullptr;
     // levels as pyramid descriptors (level 0 = the caller's image)
     PyrDesc& lev = o.lev;
     lev = PyrDesc{};
@@ -458,8 +442,7 @@ int orb_build_levels(svo_ctx* ctx, const svo_image* img, const svo_orb_params* p
         d.lv[0] = lev.lv[l];
         std::memcpy(&hdesc[l], &d, sizeof(d));
     }
-    uint32_t* dtab = (uint32_t*)(ws + o_tab);
-    PyrDesc* ddesc = o.ddesc = (PyrDesc*)(ws + o_desc);
+    PyrDesc* ddesc = o.ddesc;
     if (tab_words) SVO_HIP(ctx, hipMemcpyAsync(dtab, hst, sizeof(uint32_t) * tab_words, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(ddesc, hdesc, sizeof(PyrDesc) * nlev, hipMemcpyHostToDevice, st));
     if (mask) SVO_HIP(ctx, hipMemcpyAsync(dmask, mask, (size_t)W * H, hipMemcpyHostToDevice, st));

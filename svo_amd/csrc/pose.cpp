@@ -387,20 +387,25 @@ extern "C" int svo_solve_pnp_ransac(svo_ctx* ctx, const double* obj_xyz, const f
     std::vector<float> obj(3 * (size_t)n);
     for (size_t i = 0; i < obj.size(); i++) obj[i] = (float)obj_xyz[i];  // Point3d -> CV_32F
     const int words = (n + 31) / 32;
-    const size_t dbytes = sizeof(float) * 5 * (size_t)n + sizeof(double) * 12 * kRansacChunk +
-                          sizeof(int) * kRansacChunk + sizeof(uint32_t) * (size_t)words * kRansacChunk + 1024;
-    char* d = (char*)scratch(ctx, 5, dbytes);
-    char* h = (char*)pinned(ctx, sizeof(int) * kRansacChunk + sizeof(uint32_t) * (size_t)words * kRansacChunk +
-                                     sizeof(double) * 12 * kRansacChunk + 256);
-    if (!d || !h) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    double* dh = (double*)d;
-    int* dcnt = (int*)(dh + 12 * kRansacChunk);
-    uint32_t* dbits = (uint32_t*)(dcnt + kRansacChunk);
-    float* dobj = (float*)(dbits + (size_t)words * kRansacChunk);
-    float* dimg = dobj + 3 * (size_t)n;
-    double* hh = (double*)h;
-    int* hcnt = (int*)(hh + 12 * kRansacChunk);
-    uint32_t* hbits = (uint32_t*)(hcnt + kRansacChunk);
+    double *dh, *hh;
+    int *dcnt, *hcnt;
+    uint32_t *dbits, *hbits;
+    float *dobj, *dimg;
+    // a chunk's hypotheses, inlier counts and inlier bits, on the device and pinned
+    auto chunk = [&](Carver& c, double*& hyp, int*& cnt, uint32_t*& bits) {
+        hyp = c.take<double>(12 * kRansacChunk);
+        cnt = c.take<int>(kRansacChunk);
+        bits = c.take<uint32_t>((size_t)words * kRansacChunk);
+    };
+    auto host = [&](Carver& c) { chunk(c, hh, hcnt, hbits); };
+    void* h = pinned(ctx, layout_bytes(host));
+    if (!h || !carve_scratch(ctx, kScratchSolve, [&](Carver& c) {
+            chunk(c, dh, dcnt, dbits);
+            dobj = c.take<float>(3 * (size_t)n);
+            dimg = c.take<float>(2 * (size_t)n);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    layout_place(h, host);
     SVO_HIP(ctx, hipMemcpyAsync(dobj, obj.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(dimg, img_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
     const float thr = (float)((double)reproj_err * (double)reproj_err);
@@ -419,6 +424,7 @@ extern "C" int svo_solve_pnp_ransac(svo_ctx* ctx, const double* obj_xyz, const f
         SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
         rs.consume(hcnt, hbits, words, confidence);
     }
+    if (rs.direct) SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (n <= 5: the uploads are still in flight)
     rs.finish(K);
     if (!rs.ok) {
         if (n_inliers) *n_inliers = 0;

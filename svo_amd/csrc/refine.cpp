@@ -101,26 +101,17 @@ struct Staged {
 int stage(svo_ctx* ctx, const double* obj, const float* img, const int* counts, int P, int max_n, bool want_res,
           bool want_jac, Staged& s) {
     const size_t np = (size_t)P * max_n;
-    const size_t bytes = sizeof(double) * (3 * np + 12 * (size_t)P + (want_res ? 2 * np : 0) +
-                                           (want_jac ? 12 * np : 0) + reproj_partial_doubles(P, max_n) +
-                                           kNE * (size_t)P) +
-                         sizeof(float) * 2 * np + sizeof(int) * (size_t)P + 2048;
-    char* d = (char*)scratch(ctx, 5, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    auto carve = [&](size_t n) {
-        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
-        char* r = d;
-        d += n;
-        return r;
-    };
-    s.obj = (double*)carve(sizeof(double) * 3 * np);
-    s.poses = (double*)carve(sizeof(double) * 12 * P);
-    s.res = want_res ? (double*)carve(sizeof(double) * 2 * np) : nullptr;
-    s.jac = want_jac ? (double*)carve(sizeof(double) * 12 * np) : nullptr;
-    s.partial = (double*)carve(sizeof(double) * reproj_partial_doubles(P, max_n));
-    s.normal = (double*)carve(sizeof(double) * kNE * P);
-    s.img = (float*)carve(sizeof(float) * 2 * np);
-    s.counts = counts ? (int*)carve(sizeof(int) * P) : nullptr;
+    if (!carve_scratch(ctx, kScratchSolve, [&](Carver& c) {
+            s.obj = c.take<double>(3 * np);
+            s.poses = c.take<double>(12 * (size_t)P);
+            s.res = want_res ? c.take<double>(2 * np) : nullptr;
+            s.jac = want_jac ? c.take<double>(12 * np) : nullptr;
+            s.partial = c.take<double>(reproj_partial_doubles(P, max_n));
+            s.normal = c.take<double>(kNE * (size_t)P);
+            s.img = c.take<float>(2 * np);
+            s.counts = counts ? c.take<int>(P) : nullptr;
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     SVO_HIP(ctx, hipMemcpyAsync(s.obj, obj, sizeof(double) * 3 * np, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(s.img, img, sizeof(float) * 2 * np, hipMemcpyHostToDevice, ctx->stream));
     if (counts) SVO_HIP(ctx, hipMemcpyAsync(s.counts, counts, sizeof(int) * P, hipMemcpyHostToDevice, ctx->stream));

@@ -14,12 +14,6 @@ namespace {
 
 constexpr int kNE = kPoseRefineNE;
 
-struct Staged {
-    double *obj, *poses, *poses_out, *costs, *normal;
-    float *xy, *ur;
-    int *counts, *its;
-};
-
 const char* bad_args(const double* obj, const float* xy, const float* ur, const int* counts, int P, int max_n,
                      const double* K, double baseline, int max_iterations, const double* poses) {
     if (P < 0 || max_n < 0 || !K) return "sizes < 0 or K null";
@@ -38,51 +32,38 @@ const char* bad_args(const double* obj, const float* xy, const float* ur, const 
 // the inputs on the device (context stream) and the launch's arguments
 int stage(svo_ctx* ctx, const double* obj, const float* xy, const float* ur, const int* counts, int P, int max_n,
           const double K[9], double baseline, double huber_delta, int max_iterations, const double* poses,
-          bool separate_out, Staged& s, PoseRefineBatch& b) {
+          bool separate_out, PoseRefineBatch& b) {
     const size_t np = (size_t)P * max_n;
-    const size_t bytes = sizeof(double) * (3 * np + (12 + 12 + 2 + kNE) * (size_t)P) + sizeof(float) * 3 * np +
-                         sizeof(int) * 2 * (size_t)P + 9 * 256;
-    char* d = (char*)scratch(ctx, 14, bytes);
-    if (!d) return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
-    auto carve = [&](size_t n) {
-        d = (char*)(((uintptr_t)d + 255) & ~(uintptr_t)255);
-        char* r = d;
-        d += n;
-        return r;
-    };
-    s.obj = (double*)carve(sizeof(double) * 3 * np);
-    s.poses = (double*)carve(sizeof(double) * 12 * P);
-    s.poses_out = separate_out ? (double*)carve(sizeof(double) * 12 * P) : s.poses;
-    s.costs = (double*)carve(sizeof(double) * 2 * P);
-    s.normal = (double*)carve(sizeof(double) * kNE * P);
-    s.xy = (float*)carve(sizeof(float) * 2 * np);
-    s.ur = (float*)carve(sizeof(float) * np);
-    s.counts = counts ? (int*)carve(sizeof(int) * P) : nullptr;
-    s.its = (int*)carve(sizeof(int) * P);
+    b = PoseRefineBatch{};
+    double *d_obj, *d_poses;  // (the batch's inputs are const)
+    float *d_xy, *d_ur;
+    int* d_counts;
+    if (!carve_scratch(ctx, kScratchRefine, [&](Carver& c) {
+            b.obj = d_obj = c.take<double>(3 * np);
+            b.poses_in = d_poses = c.take<double>(12 * (size_t)P);
+            b.poses_out = separate_out ? c.take<double>(12 * (size_t)P) : d_poses;
+            b.costs = c.take<double>(2 * (size_t)P);
+            b.normal = c.take<double>(kNE * (size_t)P);
+            b.xy = d_xy = c.take<float>(2 * np);
+            b.ur = d_ur = c.take<float>(np);
+            b.counts = d_counts = counts ? c.take<int>(P) : nullptr;
+            b.iterations = c.take<int>(P);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
     hipStream_t st = ctx->stream;
     if (np) {
-        SVO_HIP(ctx, hipMemcpyAsync(s.obj, obj, sizeof(double) * 3 * np, hipMemcpyHostToDevice, st));
-        SVO_HIP(ctx, hipMemcpyAsync(s.xy, xy, sizeof(float) * 2 * np, hipMemcpyHostToDevice, st));
-        SVO_HIP(ctx, hipMemcpyAsync(s.ur, ur, sizeof(float) * np, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, hipMemcpyAsync(d_obj, obj, sizeof(double) * 3 * np, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * np, hipMemcpyHostToDevice, st));
+        SVO_HIP(ctx, hipMemcpyAsync(d_ur, ur, sizeof(float) * np, hipMemcpyHostToDevice, st));
     }
-    if (counts) SVO_HIP(ctx, hipMemcpyAsync(s.counts, counts, sizeof(int) * P, hipMemcpyHostToDevice, st));
-    SVO_HIP(ctx, hipMemcpyAsync(s.poses, poses, sizeof(double) * 12 * P, hipMemcpyHostToDevice, st));
-    b = PoseRefineBatch{};
+    if (counts) SVO_HIP(ctx, hipMemcpyAsync(d_counts, counts, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(d_poses, poses, sizeof(double) * 12 * P, hipMemcpyHostToDevice, st));
     b.P = P;
     b.cap = max_n;
-    b.poses_in = s.poses;
-    b.poses_out = s.poses_out;
-    b.counts = s.counts;
-    b.obj = s.obj;
-    b.xy = s.xy;
-    b.ur = s.ur;
     b.fx = K[0], b.fy = K[4], b.cx = K[2], b.cy = K[5];
     b.baseline = baseline;
     b.delta = huber_delta;
     b.max_iterations = max_iterations;
-    b.costs = s.costs;
-    b.iterations = s.its;
-    b.normal = s.normal;
     return SVO_OK;
 }
 
@@ -100,19 +81,18 @@ int svo_refine_poses_stereo(svo_ctx* ctx, const double* obj_xyz, const float* im
         return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_stereo: %s", why);
     if (n_problems == 0) return SVO_OK;
     const size_t P = (size_t)n_problems;
-    Staged s;
     PoseRefineBatch b;
     int rc = stage(ctx, obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, huber_delta, max_iterations,
-                   poses, false, s, b);
+                   poses, false, b);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     SVO_HIP(ctx, launch_pose_refine(b, st));
     // one block: poses_out (= poses), costs and normal are carved side by side,
     // each downloaded where the caller wants it
-    SVO_HIP(ctx, hipMemcpyAsync(poses, s.poses_out, sizeof(double) * 12 * P, hipMemcpyDeviceToHost, st));
-    if (costs) SVO_HIP(ctx, hipMemcpyAsync(costs, s.costs, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, st));
-    if (iterations) SVO_HIP(ctx, hipMemcpyAsync(iterations, s.its, sizeof(int) * P, hipMemcpyDeviceToHost, st));
-    if (normal) SVO_HIP(ctx, hipMemcpyAsync(normal, s.normal, sizeof(double) * kNE * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(poses, b.poses_out, sizeof(double) * 12 * P, hipMemcpyDeviceToHost, st));
+    if (costs) SVO_HIP(ctx, hipMemcpyAsync(costs, b.costs, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, st));
+    if (iterations) SVO_HIP(ctx, hipMemcpyAsync(iterations, b.iterations, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    if (normal) SVO_HIP(ctx, hipMemcpyAsync(normal, b.normal, sizeof(double) * kNE * P, hipMemcpyDeviceToHost, st));
     SVO_HIP(ctx, hipStreamSynchronize(st));
     return SVO_OK;
 }
@@ -127,11 +107,10 @@ int svo_refine_poses_time(svo_ctx* ctx, const double* obj_xyz, const float* img_
         return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_time: %s", why);
     if (n_problems <= 0 || max_n <= 0 || reps <= 0 || !ms_device || !ms_host)
         return set_error(ctx, SVO_ERR_ARG, "svo_refine_poses_time: bad arguments");
-    Staged s;
     PoseRefineBatch b;
     // every launch starts from the staged poses: the results go to a block of their own
     int rc = stage(ctx, obj_xyz, img_xy, img_ur, counts, n_problems, max_n, K, baseline, huber_delta, max_iterations,
-                   poses, true, s, b);
+                   poses, true, b);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     hipEvent_t e0, e1;
