@@ -263,6 +263,18 @@ int svo_match_hamming(svo_ctx* ctx, int n_problems, const int* nq, const int* nt
  * index >= nt. */
 int svo_match_filter(const int* idx_qt, const int* dist_qt, int nq, const int* idx_tq, int nt, int ratio_pct,
                      int* pairs, int cap, int* n_out);
+/* svo_match_filter on the device, for n_problems problems at once, in the layout of
+ * svo_match_hamming's outputs: idx_qt / dist_qt rows (p*q_stride + q)*2 of the
+ * forward match (nq[p] live rows, train count nt[p]), idx_tq rows (p*t_stride + t)*2
+ * of the reverse match (nt[p] live rows) or NULL for no cross-check. Per problem the
+ * kept pairs (q, t) in ascending q go to pairs[(p*q_stride + i)*2 ..], i < n_pairs[p]
+ * (at most nq[p]); rows past n_pairs[p] are not written. One block per problem, a
+ * stable compaction by wave ballots. SVO_ERR_ARG (nothing written): negative counts
+ * or ratio, a count above its stride, more than 65535 problems, null arrays, a live
+ * idx_qt entry >= nt[p]. n_problems = 0 is valid. */
+int svo_match_filter_batch(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_stride, int t_stride,
+                           const int* idx_qt, const int* dist_qt, const int* idx_tq, int ratio_pct, int* pairs,
+                           int* n_pairs);
 /* Measurement only (tools/orb_describe_bench.py): HIP-event time per launch, in ms,
  * over `reps` back-to-back launches after a warm-up, no transfers. svo_orb_describe_time:
  * detects up to cap keypoints of img (*n_kp), then ms[0] orb_blur_kernel (all levels),
@@ -892,6 +904,69 @@ int svo_frontend_refine_poses(svo_frontend* fe, double huber_delta, int max_iter
  * SVO_ERR_ARG: no stereo window enabled, called after svo_frontend_init or twice,
  * null arguments, parameters svo_stereo_match_rows rejects, guide outside 0..15. */
 int svo_frontend_set_stereo_tracking(svo_frontend* fe, const svo_stereo_rows_params* params, int guide);
+/* The place memory (opt-in; the rules: DESIGN.md section 3e): what ties a sequence
+ * that lost its features and rebuilt them in a new world frame back to the map it
+ * had. svo_frontend_init records frame t0 and every svo_frontend_step(t) with
+ * (t - t0) % every == 0 records frame t, in stream order behind the step's
+ * keyframe, without a host wait: every feature of the list the step leaves is
+ * described at octave 0 of the frame's own level-0 left image (the descriptor of
+ * svo_orb_compute with one level: cx = cvRound(x), cy = cvRound(y), moments on the
+ * frame, samples on its 7-tap blur, validity border reach), and the valid ones, in
+ * list order, go to slot k % slots of the sequence's ring (k: records since init)
+ * with their 32 descriptor bytes, their pixels and their map points' world
+ * positions: the f64 bits the map holds once the frame's own pose has moved the
+ * frame's new points to the world frame (copied behind the next step's post-LK or
+ * the next synchronize, ahead of anything that could renumber or refine them). A
+ * record keeps no map id: a later map reclaim or bundle adjustment leaves it as
+ * it is. Device memory: per sequence and slot CAP * (32 + 8 + 24) bytes plus a
+ * count, CAP = n_features rounded up to 64; and once per front end, per sequence,
+ * one blurred frame (height rows of the width rounded up to 64), CAP * (32 + 1 + 4)
+ * bytes of work and CAP * (32 + 8) bytes of query set. With streamed frames the
+ * upload into an image slot waits for the record that reads it. patch_size: odd, in
+ * [5, 31]; pattern_xy as svo_orb_compute's (NULL: svo_orb_default_pattern).
+ * Features, poses and map points are those of a front end that never made the
+ * call, bit for bit, and a front end that never makes it launches nothing more.
+ * SVO_ERR_ARG: called after svo_frontend_init or twice, slots outside
+ * 1 .. SVO_PLACES_MAX_SLOTS, every < 1, a patch_size or pattern svo_orb_compute rejects. */
+#define SVO_PLACES_MAX_SLOTS 16
+int svo_frontend_places_enable(svo_frontend* fe, int slots, int every, int patch_size, const int8_t* pattern_xy);
+/* Test view of one record (synchronises the front end first): *frame_t (-1: the
+ * slot holds none, *n = 0), *n entries, and the first min(*n, cap) of desc (32
+ * bytes each), xy (2 floats), xyz (3 doubles). Any output may be NULL.
+ * SVO_ERR_ARG: no place memory enabled, seq or slot out of range, cap < 0. */
+int svo_frontend_place(svo_frontend* fe, int seq, int slot, int* frame_t, int* n, uint8_t* desc, float* xy,
+                       double* xyz, int cap);
+/* Relocalise the frame of the last step (or of init) against the records whose
+ * frame lies in [t_lo, t_hi], for the sequences with which[s] != 0 (NULL: all);
+ * the outputs of the others are not touched. Synchronises the front end. The query
+ * set is that frame's current feature list, described, valid, compacted as a
+ * record is. Per searched record: svo_match_hamming in both directions and
+ * svo_match_filter's rule with ratio_pct and (cross_check != 0) the cross-check,
+ * for every (sequence, record) in one launch per direction and one of the filter.
+ * The best record has the most pairs, ties to the oldest frame; with fewer than
+ * max(min_pairs, 4) pairs there is no result. Otherwise svo_solve_pnp_ransac with
+ * the configuration's K, pnp_iterations, pnp_reproj, pnp_confidence on the pairs in
+ * ascending query index (the record's xyz, the query's xy): [R(rvec) | tvec] maps
+ * the record's world to the camera. Per sequence s: frame_t[s] the best record's
+ * frame (-1: no result), n_pairs[s] the best record's pair count (also when it
+ * gave no result; 0 with nothing searched), n_inliers[s], ok[s] (1: a model),
+ * rvec[3s ..], tvec[3s ..] (zero without a model). Optional (NULL to skip):
+ * slot_pairs[s*slots + k] the pair count of slot k (-1: not searched), pairs[(s*cap
+ * + i)*2 ..] the best record's pairs (query index, record index) in the compacted
+ * lists and inliers[s*cap + i] the RANSAC's inliers as indices into them, each cut
+ * to cap. SVO_ERR_ARG: no place memory enabled, before svo_frontend_init, a null
+ * required output, t_lo > t_hi, ratio_pct < 0, min_pairs < 0, cap < 0. */
+int svo_frontend_places_query(svo_frontend* fe, const uint8_t* which, int t_lo, int t_hi, int ratio_pct,
+                              int cross_check, int min_pairs, int* frame_t, int* n_pairs, int* n_inliers, int* ok,
+                              double* rvec, double* tvec, int* slot_pairs, int* pairs, int* inliers, int cap);
+/* Measurement only (tools/places_bench.py): HIP-event times in ms of ms[0] one
+ * record (blur, describe, compaction, point copy: the newest record written again
+ * from the same inputs, so nothing changes) and ms[1] a query's device half (the
+ * query set, both matches, the filter) over every sequence and the records in
+ * [t_lo, t_hi]; *n_problems (nullable): the (sequence, record) problems matched.
+ * SVO_ERR_ARG in addition to the query's: the last step's frame is not the newest record. */
+int svo_frontend_places_time(svo_frontend* fe, int t_lo, int t_hi, int ratio_pct, int cross_check, double ms[2],
+                             int* n_problems);
 /* Accumulated per-phase device time (ms) and launch counts since create/reset:
  * phases: 0 pyramid (left + Scharr), 1 lk, 2 post_lk, 3 stereo_lk, 4 pnp_score,
  * 5 tail (keyframe), 6 fast, 7 bucket, 8 append, 9 pyramid_right. Returns the number

@@ -131,6 +131,8 @@ _SIGS = [
     ("svo_orb_blur_level", C.c_int, [_vp, _vp, _vp, C.c_int, _u8p, _i32p, _i32p]),
     ("svo_match_hamming", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u8p, _u8p, _i32p, _i32p]),
     ("svo_match_filter", C.c_int, [_i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, C.c_int, _i32p]),
+    ("svo_match_filter_batch", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p, C.c_int,
+                                         _i32p, _i32p]),
     ("svo_orb_describe_time", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _f64p, _i32p]),
     ("svo_match_hamming_time", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u8p, _u8p, C.c_int, _f64p]),
     ("svo_fast_score_map", C.c_int, [_vp, _vp, C.c_int, _u8p, _u8p]),
@@ -196,6 +198,11 @@ _SIGS = [
     ("svo_frontend_window_right", C.c_int, [_vp, C.c_int, C.c_int, _f32p]),
     ("svo_frontend_bundle_adjust_stereo", C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
     ("svo_frontend_refine_poses", C.c_int, [_vp, C.c_double, C.c_int, _f64p, _i32p, _i32p]),
+    ("svo_frontend_places_enable", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i8p]),
+    ("svo_frontend_place", C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _u8p, _f32p, _f64p, C.c_int]),
+    ("svo_frontend_places_query", C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
+                                            _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i32p, C.c_int]),
+    ("svo_frontend_places_time", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _i32p]),
     ("svo_frontend_time_pyramid", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_time_fast", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_pyramid_level", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
@@ -238,6 +245,7 @@ def solve_pnp_sqpnp(obj, img_pts, K):
 
 
 ORB_DESC_BYTES = 32  # SVO_ORB_DESC_BYTES
+PLACES_MAX_SLOTS = 16  # SVO_PLACES_MAX_SLOTS
 
 
 def orb_default_pattern(patch_size: int = 31) -> np.ndarray:
@@ -736,6 +744,38 @@ class Context:
         self._check(lib().svo_match_hamming(self.handle, P, _p(nq_a, _i32p), _p(nt_a, _i32p), qs, ts, _p(q, _u8p),
                                             _p(t, _u8p), _p(idx, _i32p), _p(dist, _i32p)))
         return idx, dist
+
+    def match_filter_batch(self, idx_qt, dist_qt, nq, nt, idx_tq=None, ratio_pct: int = 80, pairs=None):
+        """svo_match_filter_batch: match_filter on the device for P problems at once, on
+        match_hamming's batched outputs: idx_qt / dist_qt (P, q_stride, 2), counts nq /
+        nt (P,), the reverse match idx_tq (P, t_stride, 2) or None for no cross-check ->
+        (pairs (P, q_stride, 2) int32, n (P,)): problem p's pairs (q, t) in ascending q
+        in rows [0, n[p]); the rows behind keep what `pairs` (given, written in place)
+        held, or -1 without it."""
+        idx_qt = _c(idx_qt, np.int32)
+        dist_qt = _c(dist_qt, np.int32)
+        if idx_qt.ndim != 3 or idx_qt.shape[2] != 2 or dist_qt.shape != idx_qt.shape:
+            raise SvoError("match_filter_batch: idx_qt / dist_qt of shape (P, q_stride, 2)")
+        P, qs = idx_qt.shape[:2]
+        nq_a, nt_a = _c(nq, np.int32).reshape(-1), _c(nt, np.int32).reshape(-1)
+        if len(nq_a) != P or len(nt_a) != P:
+            raise SvoError("match_filter_batch: one count per problem expected")
+        tq, ts = None, int(nt_a.max()) if P else 0
+        if idx_tq is not None:
+            tq = _c(idx_tq, np.int32)
+            if tq.ndim != 3 or tq.shape[0] != P or tq.shape[2] != 2:
+                raise SvoError("match_filter_batch: idx_tq of shape (P, t_stride, 2)")
+            ts = tq.shape[1]
+        if pairs is None:
+            pairs = np.full((P, qs, 2), -1, np.int32)
+        if pairs.dtype != np.int32 or pairs.shape != (P, qs, 2) or not pairs.flags.c_contiguous:
+            raise SvoError(f"match_filter_batch: pairs must be C-contiguous int32 of shape {(P, qs, 2)}")
+        n = np.zeros(max(P, 1), np.int32)
+        self._check(lib().svo_match_filter_batch(self.handle, P, _p(nq_a, _i32p), _p(nt_a, _i32p), qs, ts,
+                                                 _p(idx_qt, _i32p), _p(dist_qt, _i32p),
+                                                 None if tq is None else _p(tq, _i32p), int(ratio_pct),
+                                                 _p(pairs, _i32p), _p(n, _i32p)))
+        return pairs, n[:P]
 
     def orb_describe_time(self, img: Image, params: "OrbParams" = None, cap: int = 1 << 16, reps: int = 20):
         """Measurement only (svo_orb_describe_time): ms per launch of the blur, angle and
@@ -1452,6 +1492,67 @@ class Frontend:
         self.ctx._check(lib().svo_frontend_refine_poses(self.handle, float(huber_delta), int(max_iterations),
                                                         _p(costs, _f64p), _p(its, _i32p), _p(cnt, _i32p)))
         return costs, its, cnt
+
+    def places_enable(self, slots, every=1, patch_size=31, pattern=None):
+        """svo_frontend_places_enable: keep a ring of `slots` (1 .. PLACES_MAX_SLOTS)
+        described records per sequence, one of init's frame and of every `every`-th
+        frame after it; once, before init. pattern: (512, 2) int8 or None (the default)."""
+        keep, pp = Context._pattern_arg(pattern)  # (keep: the converted array, alive over the call)
+        self.ctx._check(lib().svo_frontend_places_enable(self.handle, int(slots), int(every), int(patch_size), pp))
+        self._places = int(slots)
+
+    def place(self, seq, slot):
+        """One record (svo_frontend_place, a test view; synchronises) -> dict of frame_t
+        (-1: none), desc (n, 32) u8, xy (n, 2) f32, xyz (n, 3) f64."""
+        cap = (self.cfg.n_features + 63) // 64 * 64
+        ft, n = C.c_int(), C.c_int()
+        desc = np.zeros((cap, ORB_DESC_BYTES), np.uint8)
+        xy = np.zeros((cap, 2), np.float32)
+        xyz = np.zeros((cap, 3), np.float64)
+        self.ctx._check(lib().svo_frontend_place(self.handle, int(seq), int(slot), C.byref(ft), C.byref(n),
+                                                 _p(desc, _u8p), _p(xy, _f32p), _p(xyz, _f64p), cap))
+        k = min(n.value, cap)
+        return {"frame_t": ft.value, "desc": desc[:k].copy(), "xy": xy[:k].copy(), "xyz": xyz[:k].copy()}
+
+    def places_query(self, t_lo=0, t_hi=(1 << 31) - 1, which=None, ratio_pct=80, cross_check=True, min_pairs=4,
+                     out=None):
+        """svo_frontend_places_query: the last step's frame against the records of the
+        frames in [t_lo, t_hi], for the sequences flagged in `which` (None: all) ->
+        dict of per-sequence arrays frame_t (-1: no result), n_pairs, n_inliers, ok,
+        rvec (S, 3), tvec (S, 3), slot_pairs (S, slots; -1: not searched), and lists
+        pairs / inliers: per sequence the best record's (query index, record index)
+        pairs and the RANSAC inliers' indices into them (empty without a result).
+        out: such a dict of a former call, whose arrays are written in place (the rows
+        of sequences outside `which` keep what they held)."""
+        S, slots = self.cfg.n_seq, getattr(self, "_places", 0) or 1
+        cap = (self.cfg.n_features + 63) // 64 * 64
+        w = None if which is None else _c(np.asarray(which).astype(np.uint8), np.uint8)
+        if w is not None and len(w) != S:
+            raise SvoError("places_query: one flag per sequence")
+        o = out if out is not None else {
+            "frame_t": np.full(S, -1, np.int32), "n_pairs": np.zeros(S, np.int32), "n_inliers": np.zeros(S, np.int32),
+            "ok": np.zeros(S, np.int32), "rvec": np.zeros((S, 3)), "tvec": np.zeros((S, 3)),
+            "slot_pairs": np.full((S, slots), -1, np.int32)}
+        pairs = np.zeros((S, cap, 2), np.int32)
+        inl = np.zeros((S, cap), np.int32)
+        self.ctx._check(lib().svo_frontend_places_query(
+            self.handle, None if w is None else _p(w, _u8p), int(t_lo), int(t_hi), int(ratio_pct), int(bool(cross_check)),
+            int(min_pairs), _p(o["frame_t"], _i32p), _p(o["n_pairs"], _i32p), _p(o["n_inliers"], _i32p),
+            _p(o["ok"], _i32p), _p(o["rvec"], _f64p), _p(o["tvec"], _f64p), _p(o["slot_pairs"], _i32p),
+            _p(pairs, _i32p), _p(inl, _i32p), cap))
+        hit = [o["frame_t"][s] >= 0 and (w is None or w[s]) for s in range(S)]
+        o["pairs"] = [pairs[s, : o["n_pairs"][s]].copy() if hit[s] else np.zeros((0, 2), np.int32) for s in range(S)]
+        o["inliers"] = [inl[s, : o["n_inliers"][s]].copy() if hit[s] else np.zeros(0, np.int32) for s in range(S)]
+        return o
+
+    def places_time(self, t_lo=0, t_hi=(1 << 31) - 1, ratio_pct=80, cross_check=True):
+        """Measurement only (svo_frontend_places_time) -> (ms of one record, ms of a
+        query's device half, the (sequence, record) problems matched)."""
+        ms = np.zeros(2, np.float64)
+        n = C.c_int()
+        self.ctx._check(lib().svo_frontend_places_time(self.handle, int(t_lo), int(t_hi), int(ratio_pct),
+                                                       int(bool(cross_check)), _p(ms, _f64p), C.byref(n)))
+        return float(ms[0]), float(ms[1]), n.value
 
     def time_pyramid(self, t, reps=20):
         """ms per pyramid + Scharr launch chain of frame t, timed alone."""

@@ -61,7 +61,8 @@ struct RectMapsDev {
 // done before the next one writes it.
 enum ScratchSlot {
     kScratchFast,       // svo_fast_score_map, svo_fast_detect: the detector's workspace
-    kScratchDescribe,   // orb_describe.cpp: the descriptor entries' blur_levels, svo_match_hamming(_time)
+    kScratchDescribe,   // orb_describe.cpp: the descriptor entries' blur_levels, svo_match_hamming(_time),
+                        // svo_match_filter_batch; frontend_places.cpp: svo_frontend_places_query / _time
     kScratchMask,       // svo_fast_detect, svo_mask_boxes: the mask
     kScratchFastOut,    // svo_fast_detect: keypoints and their count
     kScratchMaskPts,    // svo_mask_boxes: the box centres

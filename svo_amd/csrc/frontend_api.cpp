@@ -95,6 +95,9 @@ int svo_frontend_synchronize(svo_frontend* fe) {
     // the last keyframe's map points to the world frame (the next post-LK finds
     // nothing pending then)
     SVO_HIP(ctx, launch_finalize_map(fe_pending(fe), fe->S, ctx->stream));
+    // (the place memory's newest record takes its points now: they are final)
+    int rp = fe_places_flush(fe, ctx->stream);
+    if (rp) return rp;
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVO_OK;
 }

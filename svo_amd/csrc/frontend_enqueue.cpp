@@ -511,6 +511,12 @@ int fe_post(svo_frontend* fe, int t) {
     ph_end(fe, sl, slot);
     SVO_HIP(ctx, hipEventRecord(fe->ev_post, sl));
     TP("post_lk launched");
+    // the place memory: the last record's points are in the world frame now; their
+    // copy runs while the host draws hypotheses, ahead of this step's keyframe
+    {
+        int rp = fe_places_flush(fe, sl);
+        if (rp) return rp;
+    }
     if (fe->ahead.pre_pending == t + 1) {
         // (SVO_FE_PRE_AFTER_POST) frame t+1's pre-detection and right pyramid, on the
         // context stream behind this post-LK: when LK runs long, the pre-detection

@@ -459,6 +459,7 @@ void svo_frontend_destroy(svo_frontend* fe) {
     for (hipEvent_t e : fe->ev_trk)
         if (e) (void)hipEventDestroy(e);
     if (fe->trk_mem) (void)hipFree(fe->trk_mem);
+    fe_places_destroy(fe);
     if (fe->up.stage) (void)hipFree(fe->up.stage);
     if (fe->rect_stage) (void)hipFree(fe->rect_stage);
     orb_batch_destroy(fe->orb);
@@ -602,6 +603,9 @@ int svo_frontend_queue_frames(svo_frontend* fe, int t, const uint8_t* const* lef
     // frame's tracked features behind its keyframe (fe_track_stereo)
     if (fe->trk_on && fe->trk_rec[slot]) SVO_HIP(ctx, hipStreamWaitEvent(up.st, fe->ev_trk[slot], 0));
     if (fe->trk_on) fe->trk_rec[slot] = 0;
+    // ... and, with svo_frontend_places_enable, by the describe pass of that frame's record
+    if (fe->pl.slots && fe->pl.img_rec[slot]) SVO_HIP(ctx, hipStreamWaitEvent(up.st, fe->pl.ev_img[slot], 0));
+    if (fe->pl.slots) fe->pl.img_rec[slot] = 0;
     for (int side = 0; side < 2; side++) {
         const uint8_t* const* src = side ? right : left;
         uint8_t* dst = up.stage + (size_t)side * S * up.cap;
@@ -681,8 +685,13 @@ int svo_frontend_init(svo_frontend* fe, int t0) {
     fe->win.count = 0;
     rc = fe_window_record(fe, t0, ctx->stream);
     if (rc) return rc;
+    fe_places_restart(fe, t0);
+    rc = fe_places_record(fe, t0, ctx->stream);
+    if (rc) return rc;
     for (int s = 0; s < S; s++) fe_set_pose(fe, s, false, nullptr, nullptr);
     SVO_HIP(ctx, launch_finalize_map(fe_pending(fe), S, ctx->stream));
+    rc = fe_places_flush(fe, ctx->stream);
+    if (rc) return rc;
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ph_collect(fe);
     std::fill(fe->pose.begin(), fe->pose.end(), 0.0);

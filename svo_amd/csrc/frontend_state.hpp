@@ -123,6 +123,48 @@ struct FeWindow {
     float* ur_feat = nullptr;
 };
 
+// the place memory (svo_frontend_places_enable; slots == 0: off, every pointer
+// below null and nothing added to a step). Rules: DESIGN.md section 3e.
+struct FePlaces {
+    int slots = 0;           // records per sequence
+    int every = 1;           // frame t is recorded iff (t - t0) % every == 0
+    int t0 = -1;             // the init frame
+    int count = 0;           // records since init (slot of the next: count % slots)
+    std::vector<int> frame;  // [slots] frame number in each slot, -1: none yet
+    int hp = 0, reach = 0, umax[16] = {0};
+    void* mem = nullptr;  // device: everything below
+    int8_t* pat = nullptr;  // 512 (x, y)
+    // the work of one describe pass, a record's or a query's: the blurred frames
+    // [s] (planes blur_stride apart, rows blur_pitch apart), the uncompacted
+    // descriptors [s][CAP][32] and their validity [s][CAP]
+    uint8_t* blur = nullptr;
+    size_t blur_stride = 0;
+    int blur_pitch = 0;
+    uint8_t *desc_tmp = nullptr, *valid = nullptr;
+    // the ring, [s][slots][CAP] entries: descriptors, pixels, world points; n [s][slots]
+    uint8_t* desc = nullptr;
+    float* xy = nullptr;
+    double* xyz = nullptr;
+    int* n = nullptr;
+    // The newest record's map ids [s][CAP] until its points are copied: a keyframe's
+    // new points reach the world frame only when the frame's pose has landed (the
+    // next step's post-LK, or svo_frontend_synchronize), so the copy is queued
+    // right behind that (fe_places_flush) -- ahead of the next keyframe, which may
+    // renumber the ids. The record itself keeps no id.
+    int* pend_mid = nullptr;
+    bool pending = false;
+    int pend_slot = 0;
+    hipEvent_t ev_rec = nullptr;  // the newest record's compaction done (its stream)
+    // the query set: the last step's frame described and compacted, [s][CAP]; q_n [s]
+    uint8_t* q_desc = nullptr;
+    float* q_xy = nullptr;
+    int* q_n = nullptr;
+    // per image ring slot, the event behind the describe pass that read the slot's
+    // frame (a streamed upload into the slot waits for it, as for ev_trk)
+    std::vector<hipEvent_t> ev_img;
+    std::vector<char> img_rec;
+};
+
 }  // namespace svo
 
 struct svo_frontend {
@@ -132,6 +174,7 @@ struct svo_frontend {
     svo::FeAhead ahead;
     svo::FeUpload up;
     svo::FeWindow win;
+    svo::FePlaces pl;
     int S = 0, T = 0, CAP = 0, MAPCAP = 0, WORDS = 0, KCAP = 0, BCAP = 0;
     int W = 0, H = 0, nlev = 0, ml = 0, ml_st = 0;
     size_t npx = 0, bscr = 0;
@@ -301,6 +344,12 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
 PendingMap fe_pending(svo_frontend* fe);
 void fe_set_pose(svo_frontend* fe, int s, bool ok, const double rvec[3], const double tvec[3]);
 int fe_window_record(svo_frontend* fe, int t, hipStream_t st);
+// The place memory's hooks (frontend_places.cpp); each a no-op without
+// svo_frontend_places_enable. Enqueue only.
+void fe_places_restart(svo_frontend* fe, int t0);
+int fe_places_record(svo_frontend* fe, int t, hipStream_t st);
+int fe_places_flush(svo_frontend* fe, hipStream_t st);
+void fe_places_destroy(svo_frontend* fe);
 int fe_queue_full(svo_frontend* fe);
 int fe_queue_stats(svo_frontend* fe);
 double fe_finish_fits(svo_frontend* fe);

@@ -418,6 +418,9 @@ int step_keyframe_and_next(svo_frontend* fe, int t, FeStep& st) {
     // FAST chain (ev_fast) queued behind this copy
     rc = fe_window_record(fe, t, sf);
     if (rc) return rc;
+    // the place memory's record of this frame, behind it on the same terms
+    rc = fe_places_record(fe, t, sf);
+    if (rc) return rc;
     // this step's counts, before the next step's first half re-fills the mirrors
     for (int s = 0; s < S; s++) {
         st.lk_its += fe->h_itsum[s];

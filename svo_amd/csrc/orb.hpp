@@ -81,6 +81,11 @@ struct OrbDescKp {
 struct OrbDirection {  // c = m10 / hyp, s = m01 / hyp (1, 0 without a gradient)
     double c, s;
 };
+// The host tables of a descriptor pass (orb_describe.cpp): the pattern to use (the
+// caller's, checked, or the default one for a null pattern_xy) into pat[1024], the
+// hp + 1 half row widths into umax[16], the validity border into *reach. Returns
+// null, or the reason patch_size / pattern_xy are refused.
+const char* orb_describe_tables(int patch_size, const int8_t* pattern_xy, int8_t* pat, int* umax, int* reach);
 // every level of `levels` blurred into the level of the same size of `blurred`
 hipError_t launch_orb_blur(const PyrDesc& levels, const PyrDesc& blurred, hipStream_t st);
 // hp: half patch; umax: hp + 1 ints on the device
@@ -91,9 +96,24 @@ hipError_t launch_orb_angle(const PyrDesc& levels, const OrbDescKp* kp, int n, i
 hipError_t launch_orb_brief(const PyrDesc& blurred, const OrbDescKp* kp, int n, const int8_t* pattern,
                             const OrbDirection* dir, int reach, uint8_t* desc, hipStream_t st);
 // Hamming 2-NN (match.hip): problem p (blockIdx.y) matches queries q + p*q_stride*32
-// (nq[p] of them) against train t + p*t_stride*32 (nt[p]); idx / dist [p][q_stride][2]
+// (nq[p] of them) against train t + p*t_stride*32 (nt[p]); idx / dist [p][q_stride][2].
+// q_set / t_set (device, [p], nullable): problem p matches query set q_set[p]
+// against train set t_set[p] instead -- descriptors at set * stride * 32, counts
+// nq[set] / nt[set] -- and still writes rows p of idx / dist: problems that share
+// a set do not replicate it (the place memory's query, frontend_places.cpp)
 hipError_t launch_hamming_knn2(const uint32_t* q, const uint32_t* t, const int* nq, const int* nt, int q_stride,
-                               int t_stride, int n_problems, int max_nq, int* idx, int* dist, hipStream_t st);
+                               int t_stride, int n_problems, int max_nq, int* idx, int* dist, hipStream_t st,
+                               const int* q_set = nullptr, const int* t_set = nullptr);
+// svo_match_filter per problem (match_filter.hip): the ratio test and the
+// cross-check on launch_hamming_knn2's rows, then a stable compaction: the kept
+// (q, t) pairs in ascending q into pairs [p][q_stride][2], their count into
+// n_pairs[p]. idx_tq (rows [p][t_stride][2]) null: no cross-check. q_set / t_set as
+// above name the sets whose counts nq / nt bound problem p. An index outside
+// [0, nt) never passes (svo_match_filter_batch rejects it beforehand).
+hipError_t launch_match_filter(const int* idx_qt, const int* dist_qt, const int* idx_tq, const int* nq,
+                               const int* nt, int q_stride, int t_stride, int n_problems, int ratio_pct, int* pairs,
+                               int* n_pairs, hipStream_t st, const int* q_set = nullptr,
+                               const int* t_set = nullptr);
 
 hipError_t launch_orb_resize(const uint8_t* src, int spitch, const uint8_t* smask, int sw, uint8_t* dst, int dpitch,
                              uint8_t* dmask, int dw, int dh, const int* xofs, const uint32_t* xc, const int* yofs,

@@ -61,6 +61,20 @@ const char* check_describe(const svo_orb_params* prm, const int8_t* pattern_xy, 
     return nullptr;
 }
 
+}  // namespace
+
+const char* svo::orb_describe_tables(int patch_size, const int8_t* pattern_xy, int8_t* pat, int* umax, int* reach) {
+    svo_orb_params prm{};
+    prm.patch_size = patch_size;
+    prm.wta_k = 2;
+    if (const char* why = check_describe(&prm, pattern_xy, pat)) return why;
+    orb_umax(patch_size / 2, umax);
+    *reach = orb_reach(patch_size / 2);
+    return nullptr;
+}
+
+namespace {
+
 // ms per launch of `reps` back-to-back launches between two HIP events (after the
 // caller's own first launch as the warm-up); measurement entry points only
 struct TimedLoop {
@@ -366,5 +380,64 @@ extern "C" int svo_match_filter(const int* idx_qt, const int* dist_qt, int nq, c
         n++;
     }
     if (n_out) *n_out = n;
+    return SVO_OK;
+}
+
+extern "C" int svo_match_filter_batch(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_stride,
+                                      int t_stride, const int* idx_qt, const int* dist_qt, const int* idx_tq,
+                                      int ratio_pct, int* pairs, int* n_pairs) {
+    const char* who = "svo_match_filter_batch";
+    if (!ctx || n_problems < 0 || n_problems > 65535 || q_stride < 0 || t_stride < 0 || ratio_pct < 0)
+        return set_error(ctx, SVO_ERR_ARG, "%s: bad arguments", who);
+    if (n_problems == 0) return SVO_OK;
+    if (!nq || !nt || !n_pairs) return set_error(ctx, SVO_ERR_ARG, "%s: null counts", who);
+    const size_t P = (size_t)n_problems;
+    int max_nq = 0;
+    for (size_t p = 0; p < P; p++) {
+        if (nq[p] < 0 || nq[p] > q_stride || nt[p] < 0 || nt[p] > t_stride)
+            return set_error(ctx, SVO_ERR_ARG, "%s: counts of problem %zu outside [0, stride]", who, p);
+        max_nq = nq[p] > max_nq ? nq[p] : max_nq;
+    }
+    if (max_nq > 0 && (!idx_qt || !dist_qt || !pairs)) return set_error(ctx, SVO_ERR_ARG, "%s: null arrays", who);
+    for (size_t p = 0; p < P; p++)  // nothing is written on a bad index
+        for (int q = 0; q < nq[p]; q++) {
+            const int* i = idx_qt + 2 * (p * q_stride + q);
+            if (i[0] >= nt[p] || i[1] >= nt[p])
+                return set_error(ctx, SVO_ERR_ARG, "%s: an index of problem %zu is not below its train count", who, p);
+        }
+    if (max_nq == 0) {
+        std::memset(n_pairs, 0, sizeof(int) * P);
+        return SVO_OK;
+    }
+    hipStream_t st = ctx->stream;
+    const size_t qn = 2 * P * q_stride, tn = idx_tq ? 2 * P * t_stride : 0;
+    int *dqt, *ddq, *dtq, *dnq, *dnt, *dpairs, *dnp;
+    if (!carve_scratch(ctx, kScratchDescribe, [&](Carver& c) {
+            dqt = c.take<int>(qn);
+            ddq = c.take<int>(qn);
+            dtq = c.take<int>(tn);
+            dnq = c.take<int>(P);
+            dnt = c.take<int>(P);
+            dpairs = c.take<int>(qn);
+            dnp = c.take<int>(P);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
+    SVO_HIP(ctx, hipMemcpyAsync(dqt, idx_qt, sizeof(int) * qn, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(ddq, dist_qt, sizeof(int) * qn, hipMemcpyHostToDevice, st));
+    if (tn) SVO_HIP(ctx, hipMemcpyAsync(dtq, idx_tq, sizeof(int) * tn, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dnq, nq, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dnt, nt, sizeof(int) * P, hipMemcpyHostToDevice, st));
+    // (t_stride 0 with a cross-check: every nt is 0 and nothing passes the index test)
+    SVO_HIP(ctx, launch_match_filter(dqt, ddq, tn ? dtq : nullptr, dnq, dnt, q_stride, t_stride, n_problems,
+                                     ratio_pct, dpairs, dnp, st));
+    std::vector<int> hp(qn), hn(P);
+    SVO_HIP(ctx, hipMemcpyAsync(hp.data(), dpairs, sizeof(int) * qn, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(hn.data(), dnp, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    // only the rows of kept pairs reach the caller: the padding up to the stride stays as it was
+    for (size_t p = 0; p < P; p++) {
+        n_pairs[p] = hn[p];
+        std::memcpy(pairs + 2 * p * q_stride, hp.data() + 2 * p * q_stride, sizeof(int) * 2 * hn[p]);
+    }
     return SVO_OK;
 }
