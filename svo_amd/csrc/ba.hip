@@ -1,9 +1,9 @@
 // Windowed bundle adjustment: poses and points together.
 // A problem has C <= SVO_BA_MAX_CAMS cameras (world -> camera, 12 doubles,
-// reproj.hip's conventions), M points and O monocular observations (camera,
+// reproj_model.hpp's conventions), M points and O monocular observations (camera,
 // point, u, v). Per observation the residual, Huber weight, cost, Pz <= 0 rule
-// and pose Jacobian Jc (2x6, left perturbation) are reproj_kernel's; the point
-// Jacobian is Jp = Jc[:, :3] R (2x3). One Levenberg-Marquardt iteration:
+// and pose Jacobian Jc (2x6, left perturbation) are reproj_model.hpp's obs_eval;
+// the point Jacobian is Jp = Jc[:, :3] R (2x3). One Levenberg-Marquardt iteration:
 //   1 linearise   U_j = sum w Jc^T Jc, gc_j, cost (per camera); V_i = sum w Jp^T Jp,
 //                 gp_i (per point); W_ij = w Jc^T Jp is recomputed where it is used
 //   2 eliminate   V*_i = V_i + lambda diag V_i inverted in closed form,
@@ -22,8 +22,9 @@
 // observation whose right column ur is >= 0 has a third residual row, on the
 // rectified right camera at +baseline on the left camera's x axis, added behind
 // the two left rows in every sum; it weighs and costs by its 3-norm and counts
-// as two views of its point. An observation with ur < 0 has a zero third row and
-// so the monocular bits. The monocular instantiations are the code as it was.
+// as two views of its point. An observation with ur < 0 has no third row in the
+// camera sums and a zero one in the point sums, and so the monocular bits (every
+// sum here starts at +0 and adds, so a -0 term and a +0 term are the same).
 #include "ba.hpp"
 
 namespace svo {
@@ -38,76 +39,27 @@ constexpr int kEPT = (kMaxNS + kSolveThreads - 1) / kSolveThreads;  // S entries
 constexpr int kPT = 4;                            // points staged per pass of the elimination
 constexpr int kWStride = kMaxCams * 18;           // doubles of W (or Y) per staged point
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
-struct Cam {
-    double fx, fy, cx, cy, delta, bl;
-};
-
+// obs_eval for the point side: a monocular observation's r2 and third row are
+// zeroed, so point_jacobian and rows_dot may read them
 template <bool kStereo>
-constexpr int kRows = kStereo ? 3 : 2;
-
-// reproj_kernel's residual, Jacobian, weight and cost; 0 (nothing written) when
-// the point is not in front of the camera, else 1, or 2 for a stereo observation
-// (*ur >= 0): r[2] and row 2 of J are the right column's, zero for a monocular one
-template <bool kStereo>
-__device__ __forceinline__ int obs_eval(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
-                                        const float* __restrict__ u, const float* __restrict__ ur,
-                                        double& r0, double& r1, double& r2, double& w, double& cost,
-                                        double J[6 * kRows<kStereo>]) {
-    const double px = T[0] * X[0] + T[1] * X[1] + T[2] * X[2] + T[9];
-    const double py = T[3] * X[0] + T[4] * X[1] + T[5] * X[2] + T[10];
-    const double pz = T[6] * X[0] + T[7] * X[1] + T[8] * X[2] + T[11];
-    if (!(pz > 0)) return 0;
-    const double iz = 1.0 / pz, x = px * iz, y = py * iz;
-    r0 = k.fx * x + k.cx - (double)u[0];
-    r1 = k.fy * y + k.cy - (double)u[1];
-    J[0] = k.fx * iz;
-    J[1] = 0;
-    J[2] = -k.fx * x * iz;
-    J[3] = -k.fx * x * y;
-    J[4] = k.fx * (1 + x * x);
-    J[5] = -k.fx * y;
-    J[6] = 0;
-    J[7] = k.fy * iz;
-    J[8] = -k.fy * y * iz;
-    J[9] = -k.fy * (1 + y * y);
-    J[10] = k.fy * x * y;
-    J[11] = k.fy * x;
-    if constexpr (!kStereo) {
-        const double nr = sqrt(r0 * r0 + r1 * r1);
-        const bool robust = k.delta > 0 && nr > k.delta;
-        w = robust ? k.delta / nr : 1.0;
-        cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * (r0 * r0 + r1 * r1);
-        return 1;
-    } else {
-        const float urv = *ur;
-        const bool st = urv >= 0.f;
-        const double xr = (px - k.bl) * iz;
-        r2 = st ? k.fx * xr + k.cx - (double)urv : 0.0;
-        J[12] = st ? k.fx * iz : 0.0;
-        J[13] = 0;
-        J[14] = st ? -k.fx * xr * iz : 0.0;
-        J[15] = st ? -k.fx * xr * y : 0.0;
-        J[16] = st ? k.fx * (1 + xr * x) : 0.0;
-        J[17] = st ? -k.fx * y : 0.0;
-        const double n2 = (r0 * r0 + r1 * r1) + r2 * r2;
-        const double nr = sqrt(n2);
-        const bool robust = k.delta > 0 && nr > k.delta;
-        w = robust ? k.delta / nr : 1.0;
-        cost = robust ? k.delta * (nr - 0.5 * k.delta) : 0.5 * n2;
-        return st ? 2 : 1;
-    }
+__device__ __forceinline__ int obs_eval_rows(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
+                                             const float* __restrict__ u, const float* __restrict__ ur, double& r0,
+                                             double& r1, double& r2, double& w, double& cost,
+                                             double J[6 * kRows<kStereo>]) {
+    const int kind = obs_eval<kStereo>(k, T, X, u, ur, r0, r1, r2, w, cost, J);
+    if constexpr (kStereo)
+        if (kind == 1) {
+            r2 = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) J[12 + a] = 0;
+        }
+    return kind;
 }
 
 // Jp = Jc[:, :3] R (row a of Jp at Jp[3 a])
@@ -138,7 +90,7 @@ __device__ __forceinline__ double rows_dot(double w, double a0, double b0, doubl
 template <bool kFull, bool kStereo>
 __global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double* __restrict__ poses,
                                                         const double* __restrict__ points) {
-    constexpr int kN = kFull ? kBaNE : 1;
+    constexpr int kN = kFull ? kNE : 1;
     const int p = blockIdx.y, j = blockIdx.x;
     if (!d.active[p] || j >= d.n_cams[p]) return;
     const Cam k{d.fx, d.fy, d.cx, d.cy, d.delta, d.baseline};
@@ -154,19 +106,10 @@ __global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double*
         const double* X = points + 3 * ((size_t)p * d.maxM + d.cam_pt[ob + a]);
         double r0, r1, r2, w, c, J[6 * kRows<kStereo>];
         const float* ur = kStereo ? d.our + (ob + o) : nullptr;
-        if (!obs_eval<kStereo>(k, T, X, d.oxy + 2 * (ob + o), ur, r0, r1, r2, w, c, J)) continue;
+        const int kind = obs_eval<kStereo>(k, T, X, d.oxy + 2 * (ob + o), ur, r0, r1, r2, w, c, J);
+        if (!kind) continue;
         cnt++;
-        if (kFull) {
-            int q = 0;
-#pragma unroll
-            for (int a2 = 0; a2 < 6; a2++)
-#pragma unroll
-                for (int c2 = a2; c2 < 6; c2++)
-                    e[q++] += rows_dot<kStereo>(w, J[a2], J[c2], J[6 + a2], J[6 + c2], J + 12 + a2, J + 12 + c2);
-#pragma unroll
-            for (int a2 = 0; a2 < 6; a2++)
-                e[21 + a2] += rows_dot<kStereo>(w, J[a2], r0, J[6 + a2], r1, J + 12 + a2, &r2);
-        }
+        if constexpr (kFull) normal_terms<kStereo, true>(kind == 2, w, r0, r1, r2, J, e);
         e[kN - 1] += c;
     }
     __shared__ double S[4][kN];
@@ -183,9 +126,9 @@ __global__ __launch_bounds__(256) void ba_camera_kernel(BaBatch d, const double*
     const size_t cj = (size_t)p * d.maxC + j;
     if ((int)threadIdx.x < kN) {
         const int q = threadIdx.x;
-        const double s = ((S[0][q] + S[1][q]) + S[2][q]) + S[3][q];
+        const double s = wave_fold(S, q);
         if (kFull)
-            d.cam_ne[cj * kBaNE + q] = s;
+            d.cam_ne[cj * kNE + q] = s;
         else
             d.cam_cost[cj] = s;
     }
@@ -221,8 +164,8 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BaBatch d, const double* 
         const int cam = d.ocam[ob + a];
         const double* T = poses + 12 * ((size_t)p * d.maxC + cam);
         double r0, r1, r2, w, c, J[6 * kRows<kStereo>], Jp[3 * kRows<kStereo>];
-        const int kind =
-            obs_eval<kStereo>(k, T, X, d.oxy + 2 * (ob + a), kStereo ? d.our + (ob + a) : nullptr, r0, r1, r2, w, c, J);
+        const int kind = obs_eval_rows<kStereo>(k, T, X, d.oxy + 2 * (ob + a), kStereo ? d.our + (ob + a) : nullptr, r0,
+                                                r1, r2, w, c, J);
         if (!kind) continue;
         nfront += cam != prev;
         if constexpr (kStereo) {
@@ -266,7 +209,7 @@ template <bool kStereo>
 __device__ __forceinline__ void accumulate_W(const Cam& k, const double* __restrict__ T, const double* __restrict__ X,
                                              const float* __restrict__ u, const float* __restrict__ ur, double W[18]) {
     double r0, r1, r2, w, c, J[6 * kRows<kStereo>], Jp[3 * kRows<kStereo>];
-    if (!obs_eval<kStereo>(k, T, X, u, ur, r0, r1, r2, w, c, J)) return;
+    if (!obs_eval_rows<kStereo>(k, T, X, u, ur, r0, r1, r2, w, c, J)) return;
     point_jacobian<kStereo>(J, T, Jp);
 #pragma unroll
     for (int x = 0; x < 6; x++)
@@ -336,7 +279,7 @@ __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d
             offY[q] = jr * 18 + x * 3;
             offW[q] = jc * 18 + y * 3;
             if (jr == jc) {  // y <= x: entry (y, x) of the upper triangle of U
-                const double u = d.cam_ne[(cb + freecam[jr]) * kBaNE + (y * 6 - y * (y - 1) / 2 + (x - y))];
+                const double u = d.cam_ne[(cb + freecam[jr]) * kNE + (y * 6 - y * (y - 1) / 2 + (x - y))];
                 acc[q] = r == c ? u + lam * u : u;
             }
         }
@@ -417,7 +360,7 @@ __global__ __launch_bounds__(kSolveThreads) void ba_schur_solve_kernel(BaBatch d
         const int e = t + q * kSolveThreads;
         if (e < NS) Sl[e] = acc[q];
     }
-    if (t < n) bl[t] = accb - d.cam_ne[(cb + freecam[t / 6]) * kBaNE + 21 + t % 6];
+    if (t < n) bl[t] = accb - d.cam_ne[(cb + freecam[t / 6]) * kNE + 21 + t % 6];
     __syncthreads();
     if (S_out) {
         const int ld = 6 * d.maxC;
@@ -524,44 +467,7 @@ __global__ __launch_bounds__(256) void ba_point_update_kernel(BaBatch d, const d
     __syncthreads();
     if (threadIdx.x < 2) {
         const int q = threadIdx.x;
-        d.step_part[((size_t)p * gridDim.x + blockIdx.x) * 2 + q] = ((S[0][q] + S[1][q]) + S[2][q]) + S[3][q];
-    }
-}
-
-// T <- exp(xi^) T, xi = (rho, phi): refine.cpp's se3_left_update
-__device__ void se3_left_update(const double xi[6], const double* __restrict__ T, double* __restrict__ out) {
-    const double* rho = xi;
-    const double* ph = xi + 3;
-    const double th2 = (ph[0] * ph[0] + ph[1] * ph[1]) + ph[2] * ph[2];
-    const double th = sqrt(th2);
-    double A, B, Cc;  // sin/th, (1-cos)/th^2, (th-sin)/th^3
-    if (th < 1e-8) {
-        A = 1 - th2 / 6;
-        B = 0.5 - th2 / 24;
-        Cc = 1.0 / 6 - th2 / 120;
-    } else {
-        A = sin(th) / th;
-        B = (1 - cos(th)) / th2;
-        Cc = (th - sin(th)) / (th2 * th);
-    }
-    const double W[9] = {0, -ph[2], ph[1], ph[2], 0, -ph[0], -ph[1], ph[0], 0};
-    double W2[9], R[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) W2[3 * i + j] = (W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j]) + W[3 * i + 2] * W[6 + j];
-#pragma unroll
-    for (int q = 0; q < 9; q++) {
-        const double I = (q % 4 == 0);
-        R[q] = (I + A * W[q]) + B * W2[q];
-        V[q] = (I + B * W[q]) + Cc * W2[q];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const double tx = (V[3 * i] * rho[0] + V[3 * i + 1] * rho[1]) + V[3 * i + 2] * rho[2];
-#pragma unroll
-        for (int j = 0; j < 3; j++) out[3 * i + j] = (R[3 * i] * T[j] + R[3 * i + 1] * T[3 + j]) + R[3 * i + 2] * T[6 + j];
-        out[9 + i] = ((R[3 * i] * T[9] + R[3 * i + 1] * T[10]) + R[3 * i + 2] * T[11]) + tx;
+        d.step_part[((size_t)p * gridDim.x + blockIdx.x) * 2 + q] = wave_fold(S, q);
     }
 }
 

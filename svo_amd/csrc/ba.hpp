@@ -4,10 +4,9 @@
 #pragma once
 
 #include "common.hpp"
+#include "reproj_model.hpp"  // per camera, kNE sums: 21 U + 6 gc + 1 cost
 
 namespace svo {
-
-constexpr int kBaNE = 28;  // per camera: 21 U + 6 gc + 1 cost (reproj.hip's layout)
 
 // P problems, strides max_cams / max_points / max_obs per problem. Observations
 // are staged sorted by (point, camera): point i owns [pt_off[i], pt_off[i + 1])

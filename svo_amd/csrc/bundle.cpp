@@ -122,7 +122,7 @@ int alloc_staged(svo_ctx* ctx, const Sizes& a, const double* K, double delta, bo
         s.tposes = c.take<double>(12 * nC);
         s.points = c.take<double>(3 * nM);
         s.tpoints = c.take<double>(3 * nM);
-        b.cam_ne = c.take<double>(kBaNE * nC);
+        b.cam_ne = c.take<double>(kNE * nC);
         b.pt_V = c.take<double>(6 * nM);
         b.pt_g = c.take<double>(3 * nM);
         b.pt_Vinv = c.take<double>(6 * nM);
@@ -261,7 +261,7 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, const std::vector<uint8_
     const size_t P = (size_t)s.b.P;
     int rc;
     hipStream_t st = ctx->stream;
-    std::vector<double> lambda(P, 1e-4), c_trial(P), stepinfo(2 * P);
+    std::vector<double> lambda(P, kLmLambda0), c_trial(P), stepinfo(2 * P);
     std::vector<int> active(P, 1), accept(P), status(P), done(P, 0);
     c_cur.assign(P, 0.0);
     its.assign(P, 0);
@@ -295,14 +295,14 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, const std::vector<uint8_
         if ((rc = launch_solve_chain(ctx, s))) return rc;
         if ((rc = read_back())) return rc;
         // reduced system not positive definite: raise lambda and solve again from
-        // the same linearisation, as lm_solve's caller does
+        // the same linearisation, as lm_solve6's callers do
         for (;;) {
             bool retry = false;
             for (size_t p = 0; p < P; p++) {
                 const bool again = active[p] && status[p] != 0;
                 if (again) {
-                    lambda[p] *= 10;
-                    if (lambda[p] >= 1e16) {
+                    lambda[p] *= kLmUp;
+                    if (lambda[p] >= kLmCeiling) {
                         done[p] = 1;
                         active[p] = 0;
                         continue;
@@ -324,20 +324,14 @@ int run_lm(svo_ctx* ctx, Staged& s, int max_iterations, const std::vector<uint8_
         for (size_t p = 0; p < P; p++) {
             accept[p] = 0;
             if (done[p] || active[p] != 2) continue;
-            if (std::sqrt(stepinfo[2 * p]) < 1e-12 * (1 + std::sqrt(stepinfo[2 * p + 1]))) {
+            if (lm_step_is_small(stepinfo[2 * p], stepinfo[2 * p + 1])) {
                 done[p] = 1;
                 continue;
             }
-            const double c0 = c_cur[p], c1 = c_trial[p];
-            if (c1 <= c0) {
-                accept[p] = 1;
-                c_cur[p] = c1;
-                lambda[p] = lambda[p] * 0.1 > 1e-12 ? lambda[p] * 0.1 : 1e-12;
-                if (c0 - c1 <= 1e-15 * c0) done[p] = 1;
-            } else {
-                lambda[p] *= 10;
-                if (lambda[p] >= 1e16) done[p] = 1;
-            }
+            const LmVerdict v = lm_verdict(c_cur[p], c_trial[p], lambda[p]);
+            accept[p] = v.accept;
+            if (v.accept) c_cur[p] = c_trial[p];
+            done[p] = v.stop;
         }
         SVO_HIP(ctx, hipMemcpyAsync(s.accept, accept.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
         SVO_HIP(ctx, launch_ba_commit(s.b, s.accept, s.tposes, s.tpoints, s.poses, s.points, st));
@@ -661,14 +655,14 @@ static int linearize_entry(svo_ctx* ctx, const char* who, const Args& a, double 
         return dst && n ? hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) : hipSuccess;
     };
     if (U || gc) {
-        std::vector<double> ne(kBaNE * nC);
+        std::vector<double> ne(kNE * nC);
         SVO_HIP(ctx, down(ne.data(), s.b.cam_ne, sizeof(double) * ne.size()));
         for (size_t p = 0; p < P; p++)
             for (int j = 0; j < max_cams; j++) {
                 const size_t cj = p * max_cams + j;
                 const bool live = j < (n_cams ? n_cams[p] : max_cams);
-                for (int q = 0; q < 21 && U; q++) U[21 * cj + q] = live ? ne[kBaNE * cj + q] : 0;
-                for (int q = 0; q < 6 && gc; q++) gc[6 * cj + q] = live ? ne[kBaNE * cj + 21 + q] : 0;
+                for (int q = 0; q < 21 && U; q++) U[21 * cj + q] = live ? ne[kNE * cj + q] : 0;
+                for (int q = 0; q < 6 && gc; q++) gc[6 * cj + q] = live ? ne[kNE * cj + 21 + q] : 0;
             }
     }
     if (V || gp) {

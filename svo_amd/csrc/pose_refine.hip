@@ -3,13 +3,10 @@
 // with svo_bundle_adjust_stereo's observation model, run for one problem by one
 // workgroup inside a single launch (no host step between iterations).
 //
-// Per observation (include/svo_gpu.h, svo_bundle_adjust_stereo): P = R X + t,
-// the two left rows are reproj_kernel's; with ur >= 0 a third residual
-//   r2 = fx (Px - baseline) / Pz + cx - ur,  xr = (Px - baseline) / Pz,
-//   J2 = [fx/Pz, 0, -fx xr/Pz, -fx xr y, fx (1 + xr x), -fx y];
-// the Huber weight and the cost take the norm of the residual the observation
-// has; Pz <= 0 contributes nothing; ur < 0 is reproj_kernel's evaluation, term
-// by term. All arithmetic is f64.
+// The observation model (include/svo_gpu.h, svo_bundle_adjust_stereo), the 6x6
+// solve, the pose update and the LM decisions are reproj_model.hpp's: with
+// ur >= 0 its stereo evaluation, with ur < 0 (or no ur plane) the monocular one
+// that reproj_kernel runs, term by term. All arithmetic is f64.
 //
 // The 28 sums (H upper triangle 21, g 6, cost 1), in one fixed order:
 //   1. thread t adds its observations i = t, t + 256, ... in ascending i;
@@ -31,7 +28,6 @@ namespace svo {
 
 namespace {
 
-constexpr int kNE = kPoseRefineNE;
 constexpr int kBlock = 256;
 // lambda x10 from its floor 1e-12 passes 1e16 after 28 steps
 constexpr int kMaxRetry = 32;
@@ -57,12 +53,6 @@ struct Problem {
     int map_cap;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // observation i's point, null for an id outside the map
 __device__ __forceinline__ const double* point_of(const Problem& q, int i) {
     if (!q.ids) return q.pts + 3 * (size_t)i;
@@ -77,70 +67,24 @@ __device__ __forceinline__ void linearize(const PoseRefineBatch& B, const Proble
     double T[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) T[k] = Tsh[k];
-    const double fx = B.fx, fy = B.fy, cx = B.cx, cy = B.cy, delta = B.delta, bl = B.baseline;
+    const Cam cam{B.fx, B.fy, B.cx, B.cy, B.delta, B.baseline};
     double e[kNE];
     // -0 is the identity of +: the first observation's terms keep their bits
     const double first = (int)threadIdx.x < q.n ? -0.0 : 0.0;
 #pragma unroll
     for (int k = 0; k < kNE; k++) e[k] = first;
     for (int i = threadIdx.x; i < q.n; i += kBlock) {
-        double v[kNE];
-#pragma unroll
-        for (int k = 0; k < kNE; k++) v[k] = 0;
         const double* X = point_of(q, i);
-        if (X) {
-            const double px = T[0] * X[0] + T[1] * X[1] + T[2] * X[2] + T[9];
-            const double py = T[3] * X[0] + T[4] * X[1] + T[5] * X[2] + T[10];
-            const double pz = T[6] * X[0] + T[7] * X[1] + T[8] * X[2] + T[11];
-            if (pz > 0) {
-                const float2 u = q.xy[i];
-                const float urv = q.ur ? q.ur[i] : -1.f;
-                const bool st = urv >= 0.f;
-                const double iz = 1.0 / pz, x = px * iz, y = py * iz;
-                const double r0 = fx * x + cx - (double)u.x;
-                const double r1 = fy * y + cy - (double)u.y;
-                double J[18];
-                J[0] = fx * iz;
-                J[1] = 0;
-                J[2] = -fx * x * iz;
-                J[3] = -fx * x * y;
-                J[4] = fx * (1 + x * x);
-                J[5] = -fx * y;
-                J[6] = 0;
-                J[7] = fy * iz;
-                J[8] = -fy * y * iz;
-                J[9] = -fy * (1 + y * y);
-                J[10] = fy * x * y;
-                J[11] = fy * x;
-                const double xr = (px - bl) * iz;
-                const double r2 = fx * xr + cx - (double)urv;
-                J[12] = fx * iz;
-                J[13] = 0;
-                J[14] = -fx * xr * iz;
-                J[15] = -fx * xr * y;
-                J[16] = fx * (1 + xr * x);
-                J[17] = -fx * y;
-                const double n2m = r0 * r0 + r1 * r1;
-                const double n2 = st ? n2m + r2 * r2 : n2m;
-                const double nr = sqrt(n2);
-                const bool robust = delta > 0 && nr > delta;
-                const double w = robust ? delta / nr : 1.0;
-                int k = 0;
+        const float2 u = q.xy[i];
+        const float ur = q.ur ? q.ur[i] : -1.f;
+        double v[kNE], r0, r1, r2, w, J[18];
+        const int kind = X ? obs_eval<true>(cam, T, X, &u.x, &ur, r0, r1, r2, w, v[27], J) : 0;
+        if (!kind) {  // nothing to add, but +0 is added: a leading -0 becomes +0, as stated above
 #pragma unroll
-                for (int a = 0; a < 6; a++)
-#pragma unroll
-                    for (int c = a; c < 6; c++) {
-                        const double m = J[a] * J[c] + J[6 + a] * J[6 + c];
-                        v[k++] = w * (st ? m + J[12 + a] * J[12 + c] : m);
-                    }
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-                    const double m = J[a] * r0 + J[6 + a] * r1;
-                    v[21 + a] = w * (st ? m + J[12 + a] * r2 : m);
-                }
-                v[27] = robust ? delta * (nr - 0.5 * delta) : 0.5 * n2;
-            }
+            for (int k = 0; k < kNE; k++) e[k] += 0.0;
+            continue;
         }
+        normal_terms<true, false>(kind == 2, w, r0, r1, r2, J, v);
 #pragma unroll
         for (int k = 0; k < kNE; k++) e[k] += v[k];
     }
@@ -153,107 +97,9 @@ __device__ __forceinline__ void linearize(const PoseRefineBatch& B, const Proble
     __syncthreads();
     if (threadIdx.x < kNE) {
         const int k = threadIdx.x;
-        out[k] = ((S[0][k] + S[1][k]) + S[2][k]) + S[3][k];
+        out[k] = wave_fold(S, k);
     }
     __syncthreads();
-}
-
-// refine.cpp's lm_solve: (H + lambda diag(H)) x = -g by Cholesky; false if not
-// positive definite. Fully unrolled: A, L, y stay in registers.
-__device__ __forceinline__ bool lm_solve(const double* ne, double lambda, double x[6]) {
-    double A[36], b[6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int c = a; c < 6; c++) {
-                A[6 * a + c] = A[6 * c + a] = ne[k];
-                k++;
-            }
-    }
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-        A[7 * a] += lambda * (A[7 * a] > 0 ? A[7 * a] : 1e-12);
-        b[a] = -ne[21 + a];
-    }
-    double L[36];
-#pragma unroll
-    for (int k = 0; k < 36; k++) L[k] = 0;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            double s = A[6 * i + j];
-#pragma unroll
-            for (int q = 0; q < j; q++) s -= L[6 * i + q] * L[6 * j + q];
-            if (i == j) {
-                ok = ok && s > 0;
-                L[7 * i] = sqrt(ok ? s : 1.0);
-            } else {
-                L[6 * i + j] = s / L[7 * j];
-            }
-        }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int q = 0; q < i; q++) s -= L[6 * i + q] * y[q];
-        y[i] = s / L[7 * i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 6; q++) s -= L[6 * q + i] * x[q];
-        x[i] = s / L[7 * i];
-    }
-    return ok;
-}
-
-// refine.cpp's se3_left_update: Tn = exp(xi^) T, xi = (rho, phi)
-__device__ __forceinline__ void se3_left_update(const double xi[6], const double* T, double* Tn) {
-    const double* rho = xi;
-    const double* ph = xi + 3;
-    const double th2 = ph[0] * ph[0] + ph[1] * ph[1] + ph[2] * ph[2];
-    const double th = sqrt(th2);
-    double A, Bc, C;  // sin/th, (1-cos)/th^2, (th-sin)/th^3
-    if (th < 1e-8) {
-        A = 1 - th2 / 6;
-        Bc = 0.5 - th2 / 24;
-        C = 1.0 / 6 - th2 / 120;
-    } else {
-        A = sin(th) / th;
-        Bc = (1 - cos(th)) / th2;
-        C = (th - sin(th)) / (th2 * th);
-    }
-    const double W[9] = {0, -ph[2], ph[1], ph[2], 0, -ph[0], -ph[1], ph[0], 0};
-    double W2[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-    double R[9], V[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double I = (k % 4 == 0);
-        R[k] = I + A * W[k] + Bc * W2[k];
-        V[k] = I + Bc * W[k] + C * W2[k];
-    }
-    const double tx[3] = {V[0] * rho[0] + V[1] * rho[1] + V[2] * rho[2], V[3] * rho[0] + V[4] * rho[1] + V[5] * rho[2],
-                          V[6] * rho[0] + V[7] * rho[1] + V[8] * rho[2]};
-    double Ti[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) Ti[k] = T[k];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            Tn[3 * i + j] = R[3 * i] * Ti[j] + R[3 * i + 1] * Ti[3 + j] + R[3 * i + 2] * Ti[6 + j];
-        Tn[9 + i] = R[3 * i] * Ti[9] + R[3 * i + 1] * Ti[10] + R[3 * i + 2] * Ti[11] + tx[i];
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void pose_refine_kernel(PoseRefineBatch B) {
@@ -304,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void pose_refine_kernel(PoseRefineBatch B) 
         const double c = sh.ne[27];
         sh.poisoned = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) || !isfinite(c);
         sh.c_first = c;
-        sh.lambda = 1e-4;
+        sh.lambda = kLmLambda0;
         sh.its = 0;
         sh.go = 0;
     }
@@ -314,13 +160,13 @@ __global__ __launch_bounds__(kBlock) void pose_refine_kernel(PoseRefineBatch B) 
     if (!poisoned) {
         for (int it = 0; it < B.max_iterations; it++) {
             if (t == 0) {
-                // refine.cpp:195-212: solve (lambda x10 while not positive definite),
-                // the step rule, the trial pose
+                // reproj_model.hpp's LM control: solve (lambda up while not positive
+                // definite), the step rule, the trial pose
                 double lambda = sh.lambda, dx[6];
                 bool ok = false;
-                for (int r = 0; r < kMaxRetry && !ok && lambda < 1e16; r++) {
-                    ok = lm_solve(sh.ne, lambda, dx);
-                    if (!ok) lambda *= 10;
+                for (int r = 0; r < kMaxRetry && !ok && lambda < kLmCeiling; r++) {
+                    ok = lm_solve6(sh.ne, lambda, dx);
+                    if (!ok) lambda *= kLmUp;
                 }
                 sh.lambda = lambda;
                 sh.its = it + 1;
@@ -331,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void pose_refine_kernel(PoseRefineBatch B) 
                     for (int k = 0; k < 6; k++) nx += dx[k] * dx[k];
 #pragma unroll
                     for (int k = 9; k < 12; k++) nt += sh.T[k] * sh.T[k];
-                    if (!(sqrt(nx) < 1e-12 * (1 + sqrt(nt)))) {
+                    if (!lm_step_is_small(nx, nt)) {
                         se3_left_update(dx, sh.T, sh.Tt);
                         go = 1;
                     }
@@ -341,18 +187,9 @@ __global__ __launch_bounds__(kBlock) void pose_refine_kernel(PoseRefineBatch B) 
             __syncthreads();
             if (!__builtin_amdgcn_readfirstlane(sh.go)) break;  // gave up, or the step rule
             linearize(B, q, sh.Tt, sh.S, sh.nt);
-            // refine.cpp:219-228: the verdict (every thread reads the same LDS words)
-            const double c0 = sh.ne[27], c1 = sh.nt[27];
-            const bool accept = c1 <= c0;
+            // the verdict (every thread reads the same LDS words)
             double lambda = sh.lambda;
-            bool stop;
-            if (accept) {
-                lambda = lambda * 0.1 > 1e-12 ? lambda * 0.1 : 1e-12;
-                stop = c0 - c1 <= 1e-15 * c0;
-            } else {
-                lambda *= 10;
-                stop = lambda >= 1e16;
-            }
+            const auto [accept, stop] = lm_verdict(sh.ne[27], sh.nt[27], lambda);
             __syncthreads();  // c0 and lambda are read before anyone overwrites them
             if (accept) {
                 if (t < 12) sh.T[t] = sh.Tt[t];

@@ -3,10 +3,9 @@
 #pragma once
 
 #include "common.hpp"
+#include "reproj_model.hpp"
 
 namespace svo {
-
-constexpr int kPoseRefineNE = 28;  // 21 H + 6 g + 1 cost
 
 // Problem p reads its pose from poses_in and writes it to poses_out (the two may
 // be one array). Dense form (sel_nc null): pose p at 12 p, observations

@@ -3,94 +3,17 @@
 // problem with one pose block and AutoDiff reprojection residuals would solve;
 // the reference never builds one). Every iteration is one batched
 // GPU evaluation (reproj.hip) of residuals, J^T J, J^T r and cost for all
-// problems; the 6x6 solves run on the host.
-#include <cmath>
+// problems; the 6x6 solves, the pose updates and the LM decisions run on the
+// host, all three from reproj_model.hpp.
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
+#include "reproj_model.hpp"
 
 using namespace svo;
 
 namespace {
-
-constexpr int kNE = 28;
-
-// T <- exp(xi^) T, xi = (rho, phi)
-void se3_left_update(const double xi[6], double T[12]) {
-    const double* rho = xi;
-    const double* ph = xi + 3;
-    const double th2 = ph[0] * ph[0] + ph[1] * ph[1] + ph[2] * ph[2];
-    const double th = std::sqrt(th2);
-    double A, B, C;  // sin/th, (1-cos)/th^2, (th-sin)/th^3
-    if (th < 1e-8) {
-        A = 1 - th2 / 6;
-        B = 0.5 - th2 / 24;
-        C = 1.0 / 6 - th2 / 120;
-    } else {
-        A = std::sin(th) / th;
-        B = (1 - std::cos(th)) / th2;
-        C = (th - std::sin(th)) / (th2 * th);
-    }
-    const double W[9] = {0, -ph[2], ph[1], ph[2], 0, -ph[0], -ph[1], ph[0], 0};
-    double W2[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-    double R[9], V[9];
-    for (int k = 0; k < 9; k++) {
-        const double I = (k % 4 == 0);
-        R[k] = I + A * W[k] + B * W2[k];
-        V[k] = I + B * W[k] + C * W2[k];
-    }
-    const double tx[3] = {V[0] * rho[0] + V[1] * rho[1] + V[2] * rho[2], V[3] * rho[0] + V[4] * rho[1] + V[5] * rho[2],
-                          V[6] * rho[0] + V[7] * rho[1] + V[8] * rho[2]};
-    double Rn[9], tn[3];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) Rn[3 * i + j] = R[3 * i] * T[j] + R[3 * i + 1] * T[3 + j] + R[3 * i + 2] * T[6 + j];
-        tn[i] = R[3 * i] * T[9] + R[3 * i + 1] * T[10] + R[3 * i + 2] * T[11] + tx[i];
-    }
-    std::memcpy(T, Rn, sizeof(Rn));
-    std::memcpy(T + 9, tn, sizeof(tn));
-}
-
-// Solve (H + lambda diag(H)) x = -g by Cholesky; false if not positive definite.
-bool lm_solve(const double* ne, double lambda, double x[6]) {
-    double A[36], b[6];
-    int k = 0;
-    for (int a = 0; a < 6; a++)
-        for (int c = a; c < 6; c++) {
-            A[6 * a + c] = A[6 * c + a] = ne[k];
-            k++;
-        }
-    for (int a = 0; a < 6; a++) {
-        A[7 * a] += lambda * (A[7 * a] > 0 ? A[7 * a] : 1e-12);
-        b[a] = -ne[21 + a];
-    }
-    double L[36] = {0};
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            double s = A[6 * i + j];
-            for (int q = 0; q < j; q++) s -= L[6 * i + q] * L[6 * j + q];
-            if (i == j) {
-                if (!(s > 0)) return false;
-                L[7 * i] = std::sqrt(s);
-            } else {
-                L[6 * i + j] = s / L[7 * j];
-            }
-        }
-    double y[6];
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-        for (int q = 0; q < i; q++) s -= L[6 * i + q] * y[q];
-        y[i] = s / L[7 * i];
-    }
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-        for (int q = i + 1; q < 6; q++) s -= L[6 * q + i] * x[q];
-        x[i] = s / L[7 * i];
-    }
-    return true;
-}
 
 struct Staged {
     double *obj, *poses, *res, *jac, *partial, *normal;
@@ -166,7 +89,7 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
     int rc = stage(ctx, obj_xyz, img_xy, counts, P, max_n, false, false, s);
     if (rc) return rc;
     std::vector<double> cur(poses, poses + 12 * (size_t)P), trial(cur), ne(kNE * (size_t)P), ne_t(ne);
-    std::vector<double> lambda((size_t)P, 1e-4);
+    std::vector<double> lambda((size_t)P, kLmLambda0);
     std::vector<char> done((size_t)P, 0);
     auto evaluate = [&](const std::vector<double>& T, std::vector<double>& out) -> int {
         SVO_HIP(ctx, hipMemcpyAsync(s.poses, T.data(), sizeof(double) * 12 * P, hipMemcpyHostToDevice, ctx->stream));
@@ -185,9 +108,9 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
             if (done[b]) continue;
             double dx[6];
             bool ok = false;
-            while (!ok && lambda[b] < 1e16) {
-                ok = lm_solve(&ne[kNE * (size_t)b], lambda[b], dx);
-                if (!ok) lambda[b] *= 10;
+            while (!ok && lambda[b] < kLmCeiling) {
+                ok = lm_solve6(&ne[kNE * (size_t)b], lambda[b], dx);
+                if (!ok) lambda[b] *= kLmUp;
             }
             if (!ok) {
                 done[b] = 1;
@@ -196,11 +119,11 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
             double nx = 0, nt = 0;
             for (int k = 0; k < 6; k++) nx += dx[k] * dx[k];
             for (int k = 9; k < 12; k++) nt += cur[12 * (size_t)b + k] * cur[12 * (size_t)b + k];
-            if (std::sqrt(nx) < 1e-12 * (1 + std::sqrt(nt))) {
+            if (lm_step_is_small(nx, nt)) {
                 done[b] = 1;
                 continue;
             }
-            se3_left_update(dx, &trial[12 * (size_t)b]);
+            se3_left_update(dx, &trial[12 * (size_t)b], &trial[12 * (size_t)b]);
             any = true;
         }
         if (!any) break;
@@ -208,15 +131,12 @@ int svo_refine_poses(svo_ctx* ctx, const double* obj_xyz, const float* img_xy, c
         for (int b = 0; b < P; b++) {
             if (done[b]) continue;
             const double c0 = ne[kNE * (size_t)b + 27], c1 = ne_t[kNE * (size_t)b + 27];
-            if (c1 <= c0) {
+            const LmVerdict v = lm_verdict(c0, c1, lambda[b]);
+            if (v.accept) {
                 std::memcpy(&cur[12 * (size_t)b], &trial[12 * (size_t)b], sizeof(double) * 12);
                 std::memcpy(&ne[kNE * (size_t)b], &ne_t[kNE * (size_t)b], sizeof(double) * kNE);
-                lambda[b] = lambda[b] * 0.1 > 1e-12 ? lambda[b] * 0.1 : 1e-12;
-                if (c0 - c1 <= 1e-15 * c0) done[b] = 1;
-            } else {
-                lambda[b] *= 10;
-                if (lambda[b] >= 1e16) done[b] = 1;
             }
+            done[b] = v.stop;
         }
     }
     std::memcpy(poses, cur.data(), sizeof(double) * 12 * P);

@@ -12,8 +12,6 @@ using namespace svo;
 
 namespace {
 
-constexpr int kNE = kPoseRefineNE;
-
 const char* bad_args(const double* obj, const float* xy, const float* ur, const int* counts, int P, int max_n,
                      const double* K, double baseline, int max_iterations, const double* poses) {
     if (P < 0 || max_n < 0 || !K) return "sizes < 0 or K null";

@@ -3,30 +3,17 @@
 // reference links Ceres but never calls it, SURVEY §0.2, so this is pinned by
 // finite differences only). Feeds the host pose solver in refine.cpp.
 //
-// Problem b: pose T = [R|t] (world -> camera, 12 doubles, R row-major), points
-// X_i (double xyz), observations u_i (float xy), K (fx, fy, cx, cy):
-//   P = R X + t,  r = (fx Px/Pz + cx - u, fy Py/Pz + cy - v)
-//   J = dr/dxi for the left perturbation T <- exp(xi^) T, xi = (rho, phi):
-//       dP/dxi = [I | -[P]x]
-// Robust weight (Huber, delta > 0): w = 1 if |r| <= delta else delta/|r|;
-// H = sum w J^T J (21, upper triangle row-major), g = sum w J^T r (6),
-// cost = sum rho(|r|) (rho = |r|^2/2 or Huber). Points with Pz <= 0 add nothing.
+// The observation model and the layout of the 28 sums are reproj_model.hpp's;
+// this is its monocular evaluation, one thread per point.
 // Reduction: per block in a fixed order (wave shuffles, then LDS), partial sums
 // per (problem, block), then a second pass summing blocks in index order, so
 // every run gives the same bits.
 #include "common.hpp"
+#include "reproj_model.hpp"
 
 namespace svo {
 
 namespace {
-
-constexpr int kNE = 28;  // 21 H + 6 g + 1 cost
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void reproj_kernel(const double* __restrict__ obj, const float* __restrict__ img,
                                                      const int* __restrict__ counts, int cap,
@@ -43,39 +30,12 @@ __global__ __launch_bounds__(256) void reproj_kernel(const double* __restrict__ 
     if (i < n) {
         const double* X = obj + 3 * ((size_t)b * cap + i);
         const float* u = img + 2 * ((size_t)b * cap + i);
-        const double px = T[0] * X[0] + T[1] * X[1] + T[2] * X[2] + T[9];
-        const double py = T[3] * X[0] + T[4] * X[1] + T[5] * X[2] + T[10];
-        const double pz = T[6] * X[0] + T[7] * X[1] + T[8] * X[2] + T[11];
-        double r0 = 0, r1 = 0, J[12];
+        double r0 = 0, r1 = 0, r2, w, J[12];
 #pragma unroll
         for (int k = 0; k < 12; k++) J[k] = 0;
-        if (pz > 0) {
-            const double iz = 1.0 / pz, x = px * iz, y = py * iz;
-            r0 = fx * x + cx - (double)u[0];
-            r1 = fy * y + cy - (double)u[1];
-            J[0] = fx * iz;
-            J[1] = 0;
-            J[2] = -fx * x * iz;
-            J[3] = -fx * x * y;
-            J[4] = fx * (1 + x * x);
-            J[5] = -fx * y;
-            J[6] = 0;
-            J[7] = fy * iz;
-            J[8] = -fy * y * iz;
-            J[9] = -fy * (1 + y * y);
-            J[10] = fy * x * y;
-            J[11] = fy * x;
-            const double nr = sqrt(r0 * r0 + r1 * r1);
-            const double w = (delta > 0 && nr > delta) ? delta / nr : 1.0;
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++)
-#pragma unroll
-                for (int c = a; c < 6; c++) e[k++] = w * (J[a] * J[c] + J[6 + a] * J[6 + c]);
-#pragma unroll
-            for (int a = 0; a < 6; a++) e[21 + a] = w * (J[a] * r0 + J[6 + a] * r1);
-            e[27] = (delta > 0 && nr > delta) ? delta * (nr - 0.5 * delta) : 0.5 * (r0 * r0 + r1 * r1);
-        }
+        const Cam k{fx, fy, cx, cy, delta, 0};
+        if (obs_eval<false>(k, T, X, u, nullptr, r0, r1, r2, w, e[27], J))
+            normal_terms<false, false>(false, w, r0, r1, 0, J, e);
         if (res) {
             res[2 * ((size_t)b * cap + i)] = r0;
             res[2 * ((size_t)b * cap + i) + 1] = r1;
@@ -95,7 +55,7 @@ __global__ __launch_bounds__(256) void reproj_kernel(const double* __restrict__ 
     __syncthreads();
     if (threadIdx.x < kNE) {
         const int k = threadIdx.x;
-        partial[((size_t)b * gridDim.x + blockIdx.x) * kNE + k] = ((S[0][k] + S[1][k]) + S[2][k]) + S[3][k];
+        partial[((size_t)b * gridDim.x + blockIdx.x) * kNE + k] = wave_fold(S, k);
     }
 }
 

@@ -135,6 +135,12 @@ def test_all_monocular_gives_the_monocular_bits(ctx, parity_refs):
         b = call(ctx, ctx.ba_linearize, q, stereo=False, lam=LAM, huber_delta=delta)
         for k in LIN_KEYS + ("n_free", "status"):
             assert np.array_equal(bits(a[k]), bits(b[k])), (delta, k)
+        # a point on the optical axis: x = y = 0 exactly, the terms that are -0
+        q = R.batch([dict(B.on_axis(), obs_ur=np.full(1, -1.0, np.float32), baseline=R.BASELINE)])
+        a = call(ctx, ctx.ba_linearize, q, lam=LAM, huber_delta=delta)
+        b = call(ctx, ctx.ba_linearize, q, stereo=False, lam=LAM, huber_delta=delta)
+        for k in LIN_KEYS + ("n_free", "status"):
+            assert np.array_equal(bits(a[k]), bits(b[k])), (delta, k, "on the axis")
     probs = [stereo_healthy(k) for k in range(4)]
     q = R.batch(probs)
     q["obs_ur"] = np.full_like(q["obs_ur"], -1.0)

@@ -91,8 +91,13 @@ def test_linearisation_matches_the_restatement(ctx):
 @pytest.mark.parametrize("delta", [0.0, 2.0])
 def test_monocular_sums_are_the_reprojection_kernels_bits(ctx, delta):
     """n <= 256, ur all negative: the stated order is reproj_kernel's, so normal
-    equals svo_reprojection_jacobians' to the bit."""
+    equals svo_reprojection_jacobians' to the bit. The last problem sees 64 points
+    from the identity rotation, 8 of them on the optical axis (x = y = 0 exactly),
+    8 on x = 0 and 8 on y = 0: the terms that are -0."""
     probs = [problem(n, 50 + k) for k, n in enumerate([1, 64, 200, 256])]
+    X, xy, _, _ = problem(64, 54)
+    X[:8, :2], X[8:16, 0], X[16:24, 1] = 0.0, 0.0, 0.0
+    probs.append((X, xy, None, np.r_[np.eye(3).ravel(), 0.0, 0.0, 0.5]))
     probs = [(X, xy, np.full(len(X), -1.0, np.float32), T0) for X, xy, _, T0 in probs]
     X, xy, ur, T, counts = batch(probs)
     _, _, _, ne = run(ctx, probs, delta=delta, iters=0)
