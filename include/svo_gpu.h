@@ -284,6 +284,56 @@ int svo_orb_describe_time(svo_ctx* ctx, const svo_image* img, const svo_orb_para
                           double ms[3], int* n_kp);
 int svo_match_hamming_time(svo_ctx* ctx, int n_problems, const int* nq, const int* nt, int q_stride, int t_stride,
                            const uint8_t* q, const uint8_t* t, int reps, double* ms);
+/* Matching map points to a frame by projection: where
+ * ORBmatcher::SearchByProjection would stand in a port. Problem p of n_problems
+ * has n_pts[p] points xyz + (p*p_stride + i)*3 (f64, world) with descriptors pdesc
+ * + (p*p_stride + i)*32, n_kp[p] keypoints kxy + (p*k_stride + j)*2 (f32 pixels)
+ * with descriptors kdesc + (p*k_stride + j)*32, and a pose poses + 12 p: T = [R
+ * row-major | t], world -> camera. K4 = (fx, fy, cx, cy); w x h: the frame.
+ *  1. Projection, f64, in this order: px = T0 X + T1 Y + T2 Z + T9 summed left to
+ *     right, py (T3 T4 T5 T10) and pz (T6 T7 T8 T11) likewise; iz = 1 / pz,
+ *     u = fx (px iz) + cx, v = fy (py iz) + cy; uf = (float)u, vf = (float)v.
+ *     proj = (uf, vf) if pz > 0, else (-1, -1). The point is visible iff pz > 0 and
+ *     0 <= uf < (float)w and 0 <= vf < (float)h (a NaN fails).
+ *  2. Keypoint j is usable iff 0 <= kx < (float)w and 0 <= ky < (float)h (a NaN is
+ *     not). It is a candidate of a visible point iff it is usable and fabsf(kx - uf)
+ *     <= radius and fabsf(ky - vf) <= radius in f32: a square window, edge included.
+ *  3. d = popcount(pdesc_i xor kdesc_j). The best candidate is the smallest (d, j)
+ *     taken lexicographically, the second best the next smallest: idx[(p*p_stride +
+ *     i)*2 + k] and dist[...] as svo_match_hamming's, a missing neighbour -1 / 257; a
+ *     point that is not visible or has no candidate gets (-1, -1) and (257, 257).
+ *  4. Point i bids for j = idx[i][0] iff j >= 0, dist[i][0] <= max_dist, and
+ *     ratio_pct == 0 or there is no second neighbour or dist[i][0] * 100 < ratio_pct
+ *     * dist[i][1] (a single candidate passes). Each keypoint goes to the bidder
+ *     with the smallest (d, i). pairs[(p*k_stride + k)*2 ..] = (j, i) in ascending
+ *     j, k < n_pairs[p]: the keypoint first, as the frame comes first in
+ *     svo_frontend_places_query's pairs.
+ * Nothing depends on the search structure: every choice is a minimum over keys.
+ * Rows past the counts are not written. Any of idx, dist, proj, pairs may be NULL
+ * to skip it; n_pairs is required with pairs. SVO_ERR_ARG (nothing written): a null
+ * context or params, negative counts, a count above its stride, more than 65535
+ * problems, a stride above 2^20, w or h < 1, radius not finite or <= 0, max_dist
+ * outside [0, 256], ratio_pct < 0, a null required array while any count is
+ * positive. n_problems = 0 is valid. */
+typedef struct svo_proj_match_params {
+    float radius;  /* half side of the search window in pixels; default 4 */
+    int max_dist;  /* a best distance above this does not bid; default 64 */
+    int ratio_pct; /* ratio test in percent, 0 = off; default 80 */
+} svo_proj_match_params;
+int svo_match_projected(svo_ctx* ctx, int n_problems, const int* n_pts, const int* n_kp, int p_stride, int k_stride,
+                        const double* xyz, const uint8_t* pdesc, const float* kxy, const uint8_t* kdesc,
+                        const double* poses, const double* K4, int w, int h, const svo_proj_match_params* params,
+                        int* idx, int* dist, float* proj, int* pairs, int* n_pairs);
+/* Measurement only (tools/match_projected_bench.py), as svo_match_hamming_time: ms
+ * per launch of ms[0] proj_bin_kernel, ms[1] proj_match_kernel, ms[2]
+ * proj_pairs_kernel on the uploaded problems. */
+int svo_match_projected_time(svo_ctx* ctx, int n_problems, const int* n_pts, const int* n_kp, int p_stride,
+                             int k_stride, const double* xyz, const uint8_t* pdesc, const float* kxy,
+                             const uint8_t* kdesc, const double* poses, const double* K4, int w, int h,
+                             const svo_proj_match_params* params, int reps, double ms[3]);
+/* T = [R(rvec) | tvec] as svo_match_projected takes it (cv::Rodrigues; host only,
+ * no context): what svo_solve_pnp_ransac returns, turned into a pose. */
+int svo_pose_from_rvec(const double rvec[3], const double tvec[3], double T[12]);
 
 /* R:src/tracking.cpp:76-79: W*H mask of 255 with a filled box of +-half around
  * each point (cvRound corners, inclusive, clipped). Host output. */
@@ -967,6 +1017,24 @@ int svo_frontend_places_query(svo_frontend* fe, const uint8_t* which, int t_lo, 
  * SVO_ERR_ARG in addition to the query's: the last step's frame is not the newest record. */
 int svo_frontend_places_time(svo_frontend* fe, int t_lo, int t_hi, int ratio_pct, int cross_check, double ms[2],
                              int* n_problems);
+/* The second look at a query's pose, for every sequence
+ * with which[s] != 0 (NULL: all) and frame_t[s] >= 0; the outputs of the others
+ * are not touched. The record of frame frame_t[s] is projected under [R(rvec + 3s)
+ * | tvec + 3s] and matched by svo_match_projected's rules (the configuration's K,
+ * the frame's size, params) against the query set of the last step's frame, built
+ * as svo_frontend_places_query builds it; all sequences in one launch chain. Then
+ * svo_solve_pnp_ransac with the front end's PnP settings on the widened pairs in
+ * ascending query index (the record's xyz, the query's xy). Synchronises the front
+ * end and writes nothing into it. Per sequence: n_pairs[s], n_inliers[s], ok[s],
+ * rvec_out[3s ..], tvec_out[3s ..] (zero without a model; they may alias rvec /
+ * tvec); optional pairs[(s*cap + i)*2 ..] = (query index, record index) and
+ * inliers[s*cap + i] as the query's, each cut to cap. A sequence whose frame_t is
+ * no longer in its ring, or with fewer than 4 pairs, gets ok = 0 (and n_pairs = 0
+ * for the former). SVO_ERR_ARG: as the query's, a null frame_t / rvec / tvec, and
+ * params svo_match_projected rejects. */
+int svo_frontend_places_widen(svo_frontend* fe, const uint8_t* which, const int* frame_t, const double* rvec,
+                              const double* tvec, const svo_proj_match_params* params, int* n_pairs, int* n_inliers,
+                              int* ok, double* rvec_out, double* tvec_out, int* pairs, int* inliers, int cap);
 /* Accumulated per-phase device time (ms) and launch counts since create/reset:
  * phases: 0 pyramid (left + Scharr), 1 lk, 2 post_lk, 3 stereo_lk, 4 pnp_score,
  * 5 tail (keyframe), 6 fast, 7 bucket, 8 append, 9 pyramid_right. Returns the number

@@ -135,6 +135,11 @@ _SIGS = [
                                          _i32p, _i32p]),
     ("svo_orb_describe_time", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _f64p, _i32p]),
     ("svo_match_hamming_time", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u8p, _u8p, C.c_int, _f64p]),
+    ("svo_match_projected", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _f64p, _u8p, _f32p, _u8p, _f64p,
+                                      _f64p, C.c_int, C.c_int, _vp, _i32p, _i32p, _f32p, _i32p, _i32p]),
+    ("svo_match_projected_time", C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _f64p, _u8p, _f32p, _u8p,
+                                           _f64p, _f64p, C.c_int, C.c_int, _vp, C.c_int, _f64p]),
+    ("svo_pose_from_rvec", C.c_int, [_f64p, _f64p, _f64p]),
     ("svo_fast_score_map", C.c_int, [_vp, _vp, C.c_int, _u8p, _u8p]),
     ("svo_mask_boxes", C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_float, _u8p]),
     ("svo_bucket_features", C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -203,6 +208,8 @@ _SIGS = [
     ("svo_frontend_places_query", C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p,
                                             _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i32p, C.c_int]),
     ("svo_frontend_places_time", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _i32p]),
+    ("svo_frontend_places_widen", C.c_int, [_vp, _u8p, _i32p, _f64p, _f64p, _vp, _i32p, _i32p, _i32p, _f64p, _f64p,
+                                            _i32p, _i32p, C.c_int]),
     ("svo_frontend_time_pyramid", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_time_fast", C.c_int, [_vp, C.c_int, C.c_int, _f64p]),
     ("svo_frontend_pyramid_level", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
@@ -287,6 +294,17 @@ def match_filter(idx_qt, dist_qt, idx_tq=None, ratio_pct: int = 80, cap=None) ->
     if rc != 0:
         raise SvoError("svo_match_filter: bad arguments (negative ratio, or an index past the reverse match)")
     return pairs[: min(n.value, cap)].copy()
+
+
+def pose_from_rvec(rvec, tvec) -> np.ndarray:
+    """svo_pose_from_rvec: T = [R(rvec) row-major | tvec], 12 doubles, world -> camera:
+    a pose as match_projected takes it. Host code of the library; no GPU context."""
+    rv = _c(rvec, np.float64).reshape(3)
+    tv = _c(tvec, np.float64).reshape(3)
+    T = np.empty(12, np.float64)
+    if lib().svo_pose_from_rvec(_p(rv, _f64p), _p(tv, _f64p), _p(T, _f64p)) != 0:
+        raise SvoError("svo_pose_from_rvec: bad arguments")
+    return T
 
 
 class PinnedBuffer:
@@ -529,6 +547,15 @@ class StereoRowsParams(C.Structure):
 
     def __init__(self, radius=5, d_min=-1, d_max=128, uniq_pct=80, max_cost=0):
         super().__init__(int(radius), int(d_min), int(d_max), int(uniq_pct), int(max_cost))
+
+
+class ProjMatchParams(C.Structure):
+    """svo_proj_match_params (include/svo_gpu.h): the search window's half side in
+    pixels, the largest distance that bids, the ratio test in percent (0 = off)."""
+    _fields_ = [("radius", C.c_float), ("max_dist", C.c_int), ("ratio_pct", C.c_int)]
+
+    def __init__(self, radius=4.0, max_dist=64, ratio_pct=80):
+        super().__init__(float(radius), int(max_dist), int(ratio_pct))
 
 
 class Context:
@@ -823,6 +850,107 @@ class Context:
         if not ok:
             raise SvoError("relocalize: RANSAC found no pose")
         return rvec, tvec, pairs[inl]
+
+    def _proj_args(self, who, xyz, pdesc, kxy, kdesc, pose, K, size, n_pts, n_kp):
+        xyz = _c(xyz, np.float64)
+        pdesc = _c(pdesc, np.uint8)
+        kxy = _c(kxy, np.float32)
+        kdesc = _c(kdesc, np.uint8)
+        pose = _c(pose, np.float64)
+        K = _c(K, np.float64).reshape(-1)
+        K4 = K if len(K) == 4 else _c(K.reshape(9)[[0, 4, 2, 5]], np.float64)
+        w, h = int(size[0]), int(size[1])
+        if n_pts is None and n_kp is None:
+            xyz, pdesc = xyz.reshape(-1, 3), pdesc.reshape(-1, ORB_DESC_BYTES)
+            kxy, kdesc = kxy.reshape(-1, 2), kdesc.reshape(-1, ORB_DESC_BYTES)
+            P, ps, ks = 1, len(xyz), len(kxy)
+            np_a, nk_a = np.array([ps], np.int32), np.array([ks], np.int32)
+            lead = ()
+        else:
+            if xyz.ndim != 3 or pdesc.ndim != 3 or kxy.ndim != 3 or kdesc.ndim != 3 or n_pts is None or n_kp is None:
+                raise SvoError(f"{who}: batched form takes xyz (P, p_stride, 3), pdesc (P, p_stride, 32), "
+                               "kxy (P, k_stride, 2), kdesc (P, k_stride, 32), n_pts, n_kp")
+            P, ps, ks = len(xyz), xyz.shape[1], kxy.shape[1]
+            np_a, nk_a = _c(n_pts, np.int32).reshape(-1), _c(n_kp, np.int32).reshape(-1)
+            if len(np_a) != P or len(nk_a) != P or len(kxy) != P:
+                raise SvoError(f"{who}: one count per problem expected")
+            lead = (P,)
+        if xyz.shape != lead + (ps, 3) or pdesc.shape != lead + (ps, ORB_DESC_BYTES) or \
+                kxy.shape != lead + (ks, 2) or kdesc.shape != lead + (ks, ORB_DESC_BYTES) or pose.size != 12 * P:
+            raise SvoError(f"{who}: one descriptor per point and per keypoint, 12 pose doubles per problem expected")
+        return xyz, pdesc, kxy, kdesc, pose, K4, w, h, P, ps, ks, np_a, nk_a, lead
+
+    def match_projected(self, xyz, pdesc, kxy, kdesc, pose, K, size, params: "ProjMatchParams" = None, n_pts=None,
+                        n_kp=None, idx=None, dist=None, proj=None, pairs=None):
+        """svo_match_projected: the points xyz (f64, world) with
+        descriptors pdesc projected under pose (12 doubles [R row-major | t], world ->
+        camera: pose_from_rvec) and K (3x3, or (fx, fy, cx, cy)) into a frame of size =
+        (w, h), each matched against the keypoints kxy / kdesc inside a window of
+        +-params.radius. Single sets: xyz (n, 3), kxy (m, 2) -> (idx (n, 2), dist (n, 2),
+        proj (n, 2) f32, pairs (m, 2), n_pairs): best then second-best keypoint of every
+        point (a missing one -1 / 257), the projections, and the pairs (keypoint, point)
+        in ascending keypoint, rows [0, n_pairs). Batched: (P, stride, ...) arrays with
+        counts n_pts, n_kp (P,), pose (P, 12) -> (P, stride, 2) arrays and n_pairs (P,).
+        Rows past the counts keep what idx / dist / proj / pairs (given, written in
+        place) held, or -1 (257 for dist) without them."""
+        who = "match_projected"
+        params = params or ProjMatchParams()
+        xyz, pdesc, kxy, kdesc, pose, K4, w, h, P, ps, ks, np_a, nk_a, lead = self._proj_args(
+            who, xyz, pdesc, kxy, kdesc, pose, K, size, n_pts, n_kp)
+        outs = []
+        for name, a, rows, dt, fill in (("idx", idx, ps, np.int32, -1), ("dist", dist, ps, np.int32, 257),
+                                        ("proj", proj, ps, np.float32, -1), ("pairs", pairs, ks, np.int32, -1)):
+            shape = lead + (rows, 2)
+            if a is None:
+                a = np.full(shape, fill, dt)
+            if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise SvoError(f"{who}: {name} must be C-contiguous {np.dtype(dt).name} of shape {shape}")
+            outs.append(a)
+        idx, dist, proj, pairs = outs
+        n = np.zeros(max(P, 1), np.int32)
+        self._check(lib().svo_match_projected(
+            self.handle, P, _p(np_a, _i32p), _p(nk_a, _i32p), ps, ks, _p(xyz, _f64p), _p(pdesc, _u8p), _p(kxy, _f32p),
+            _p(kdesc, _u8p), _p(pose, _f64p), _p(K4, _f64p), w, h, C.addressof(params), _p(idx, _i32p),
+            _p(dist, _i32p), _p(proj, _f32p), _p(pairs, _i32p), _p(n, _i32p)))
+        return idx, dist, proj, pairs, (n[:P] if lead else int(n[0]))
+
+    def match_projected_time(self, xyz, pdesc, kxy, kdesc, pose, K, size, n_pts, n_kp,
+                             params: "ProjMatchParams" = None, reps: int = 10) -> np.ndarray:
+        """Measurement only (svo_match_projected_time): ms per launch of the bin, match
+        and pairs kernels on the batch (match_projected's batched form) -> (3,)."""
+        params = params or ProjMatchParams()
+        xyz, pdesc, kxy, kdesc, pose, K4, w, h, P, ps, ks, np_a, nk_a, _ = self._proj_args(
+            "match_projected_time", xyz, pdesc, kxy, kdesc, pose, K, size, n_pts, n_kp)
+        ms = np.zeros(3, np.float64)
+        self._check(lib().svo_match_projected_time(
+            self.handle, P, _p(np_a, _i32p), _p(nk_a, _i32p), ps, ks, _p(xyz, _f64p), _p(pdesc, _u8p), _p(kxy, _f32p),
+            _p(kdesc, _u8p), _p(pose, _f64p), _p(K4, _f64p), w, h, C.addressof(params), int(reps), _p(ms, _f64p)))
+        return ms
+
+    def relocalize_guided(self, map_desc, map_xyz, desc, kp_xy, K, size, params: "ProjMatchParams" = None,
+                          **relocalize_kw):
+        """relocalize, then the second look every ORB-style system takes before it
+        accepts such a pose: match_projected of the whole map under the first pose
+        into the frame of size = (w, h), and solve_pnp_ransac (relocalize's iterations,
+        reproj_err, confidence) on the widened pairs in ascending frame index ->
+        (rvec, tvec, inlier pairs (m, 2) of (frame index, map index), first), first =
+        relocalize's own (rvec, tvec, inlier pairs). SvoError as relocalize's, and when
+        fewer than 4 widened pairs remain or their RANSAC finds no model."""
+        first = self.relocalize(map_desc, map_xyz, desc, kp_xy, K, **relocalize_kw)
+        map_desc = _c(map_desc, np.uint8).reshape(-1, ORB_DESC_BYTES)
+        desc = _c(desc, np.uint8).reshape(-1, ORB_DESC_BYTES)
+        map_xyz = _c(map_xyz, np.float64).reshape(-1, 3)
+        kp_xy = _c(np.asarray(kp_xy, np.float32).reshape(len(desc), -1)[:, :2], np.float32)
+        _, _, _, pairs, n = self.match_projected(map_xyz, map_desc, kp_xy, desc, pose_from_rvec(first[0], first[1]), K,
+                                                 size, params)
+        pairs = pairs[:n]
+        if n < 4:
+            raise SvoError(f"relocalize_guided: {n} widened pairs, 4 needed")
+        rkw = {k: relocalize_kw[k] for k in ("iterations", "reproj_err", "confidence") if k in relocalize_kw}
+        ok, rvec, tvec, inl = self.solve_pnp_ransac(map_xyz[pairs[:, 1]], kp_xy[pairs[:, 0]], K, **rkw)
+        if not ok:
+            raise SvoError("relocalize_guided: RANSAC found no pose on the widened pairs")
+        return rvec, tvec, pairs[inl], first
 
     def fast_score_map(self, img: Image, threshold: int = 20):
         score = np.empty((img.h, img.w), np.uint8)
@@ -1543,6 +1671,36 @@ class Frontend:
         hit = [o["frame_t"][s] >= 0 and (w is None or w[s]) for s in range(S)]
         o["pairs"] = [pairs[s, : o["n_pairs"][s]].copy() if hit[s] else np.zeros((0, 2), np.int32) for s in range(S)]
         o["inliers"] = [inl[s, : o["n_inliers"][s]].copy() if hit[s] else np.zeros(0, np.int32) for s in range(S)]
+        return o
+
+    def places_widen(self, result, params: "ProjMatchParams" = None, which=None):
+        """svo_frontend_places_widen: the second look at places_query's poses. result:
+        places_query's return value; every sequence flagged in `which` (None: all) with
+        result["frame_t"][s] >= 0 has that frame's record projected under the query's
+        pose and matched by match_projected's rules against the last step's frame,
+        then solve_pnp_ransac on the widened pairs -> dict of per-sequence arrays
+        n_pairs, n_inliers, ok, rvec (S, 3), tvec (S, 3) (zero rows for the sequences
+        left out) and lists pairs (query index, record index) / inliers."""
+        S = self.cfg.n_seq
+        cap = (self.cfg.n_features + 63) // 64 * 64
+        params = params or ProjMatchParams()
+        w = None if which is None else _c(np.asarray(which).astype(np.uint8), np.uint8)
+        if w is not None and len(w) != S:
+            raise SvoError("places_widen: one flag per sequence")
+        ft = _c(result["frame_t"], np.int32).reshape(-1)
+        rv, tv = _c(result["rvec"], np.float64), _c(result["tvec"], np.float64)
+        if len(ft) != S or rv.shape != (S, 3) or tv.shape != (S, 3):
+            raise SvoError("places_widen: result must be places_query's return value")
+        o = {"n_pairs": np.zeros(S, np.int32), "n_inliers": np.zeros(S, np.int32), "ok": np.zeros(S, np.int32),
+             "rvec": np.zeros((S, 3)), "tvec": np.zeros((S, 3))}
+        pairs = np.zeros((S, cap, 2), np.int32)
+        inl = np.zeros((S, cap), np.int32)
+        self.ctx._check(lib().svo_frontend_places_widen(
+            self.handle, None if w is None else _p(w, _u8p), _p(ft, _i32p), _p(rv, _f64p), _p(tv, _f64p),
+            C.addressof(params), _p(o["n_pairs"], _i32p), _p(o["n_inliers"], _i32p), _p(o["ok"], _i32p),
+            _p(o["rvec"], _f64p), _p(o["tvec"], _f64p), _p(pairs, _i32p), _p(inl, _i32p), cap))
+        o["pairs"] = [pairs[s, : o["n_pairs"][s]].copy() for s in range(S)]
+        o["inliers"] = [inl[s, : o["n_inliers"][s]].copy() for s in range(S)]
         return o
 
     def places_time(self, t_lo=0, t_hi=(1 << 31) - 1, ratio_pct=80, cross_check=True):

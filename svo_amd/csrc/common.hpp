@@ -62,7 +62,8 @@ struct RectMapsDev {
 enum ScratchSlot {
     kScratchFast,       // svo_fast_score_map, svo_fast_detect: the detector's workspace
     kScratchDescribe,   // orb_describe.cpp: the descriptor entries' blur_levels, svo_match_hamming(_time),
-                        // svo_match_filter_batch; frontend_places.cpp: svo_frontend_places_query / _time
+                        // svo_match_filter_batch; match_projected.cpp: svo_match_projected(_time);
+                        // frontend_places.cpp: svo_frontend_places_query / _time / _widen
     kScratchMask,       // svo_fast_detect, svo_mask_boxes: the mask
     kScratchFastOut,    // svo_fast_detect: keypoints and their count
     kScratchMaskPts,    // svo_mask_boxes: the box centres

@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "frontend_state.hpp"
+#include "linalg.hpp"
+#include "match_projected.hpp"
 #include "places.hpp"
 
 namespace svo {
@@ -110,7 +112,7 @@ namespace {
 struct PlacesWork {
     std::vector<int> seq, slot;  // per problem
     int *q_set, *t_set;          // device [P]: the query set (s) and the record (s * slots + slot)
-    int *idx_qt, *dist_qt, *idx_tq, *dist_tq;  // [P][CAP][2]
+    int *idx_qt, *dist_qt, *idx_tq, *dist_tq;  // [P][CAP][2] (the query alone)
     int *pairs, *n_pairs;                      // [P][CAP][2], [P]
     int *sel_prob, *sel_q, *sel_rec;           // [S] the chosen problems
     double* obj;                               // [S][CAP][3]
@@ -149,6 +151,19 @@ int places_problems(svo_frontend* fe, const uint8_t* which, int t_lo, int t_hi, 
     return SVO_OK;
 }
 
+// The query set of every sequence on stream st: the last step's frame described
+// and compacted into q_desc / q_xy / q_n.
+int places_query_set(svo_frontend* fe, hipStream_t st) {
+    FePlaces& pl = fe->pl;
+    const int CAP = fe->CAP;
+    int rc = places_describe(fe, fe->ahead.stepped, st);
+    if (rc) return rc;
+    PlacesCompact c{fe->nA,  pl.valid, pl.desc_tmp, fe->xyA, nullptr, CAP, pl.q_desc,
+                    pl.q_xy, nullptr, (size_t)CAP, pl.q_n, 1};
+    SVO_HIP(fe->ctx, launch_places_compact(c, fe->S, st));
+    return SVO_OK;
+}
+
 // The device half of a query on the context stream: the query set (the last
 // step's frame described and compacted), the 2-NN of every problem in both
 // directions -- a sequence's problems share its query set in place -- and the filter.
@@ -158,11 +173,8 @@ int places_match(svo_frontend* fe, const PlacesWork& w, const int* h_q_set, cons
     FePlaces& pl = fe->pl;
     hipStream_t st = ctx->stream;
     const int P = (int)w.seq.size(), CAP = fe->CAP;
-    int rc = places_describe(fe, fe->ahead.stepped, st);
+    int rc = places_query_set(fe, st);
     if (rc) return rc;
-    PlacesCompact c{fe->nA,  pl.valid, pl.desc_tmp, fe->xyA, nullptr, CAP, pl.q_desc,
-                    pl.q_xy, nullptr, (size_t)CAP, pl.q_n, 1};
-    SVO_HIP(ctx, launch_places_compact(c, fe->S, st));
     if (P == 0) return SVO_OK;
     SVO_HIP(ctx, hipMemcpyAsync(w.q_set, h_q_set, sizeof(int) * P, hipMemcpyHostToDevice, st));
     SVO_HIP(ctx, hipMemcpyAsync(w.t_set, h_t_set, sizeof(int) * P, hipMemcpyHostToDevice, st));
@@ -378,6 +390,134 @@ int svo_frontend_places_query(svo_frontend* fe, const uint8_t* which, int t_lo, 
         n_inliers[s] = found ? ni : 0;
         if (!found)
             for (int q = 0; q < 3; q++) rvec[3 * s + q] = tvec[3 * s + q] = 0.0;
+        if (inliers && found) std::memcpy(inliers + (size_t)s * cap, inl.data(), sizeof(int) * std::min(ni, cap));
+    }
+    return SVO_OK;
+}
+
+int svo_frontend_places_widen(svo_frontend* fe, const uint8_t* which, const int* frame_t, const double* rvec,
+                              const double* tvec, const svo_proj_match_params* params, int* n_pairs, int* n_inliers,
+                              int* ok, double* rvec_out, double* tvec_out, int* pairs, int* inliers, int cap) {
+    const char* who = "svo_frontend_places_widen";
+    if (!fe) return SVO_ERR_ARG;
+    svo_ctx* ctx = fe->ctx;
+    if (!frame_t || !rvec || !tvec || !n_pairs || !n_inliers || !ok || !rvec_out || !tvec_out || cap < 0)
+        return set_error(ctx, SVO_ERR_ARG, "%s: null arguments or cap < 0", who);
+    int rc = places_query_check(fe, 0, 0, 0, 0, who);
+    if (rc) return rc;
+    if (const char* why = proj_params_refused(fe->W, fe->H, params))
+        return set_error(ctx, SVO_ERR_ARG, "%s: %s", who, why);
+    if (fe->CAP > kProjMaxStride) return set_error(ctx, SVO_ERR_ARG, "%s: more than 2^20 features per sequence", who);
+    rc = svo_frontend_synchronize(fe);
+    if (rc) return rc;
+    const FePlaces& pl = fe->pl;
+    const svo_frontend_config& cfg = fe->cfg;
+    hipStream_t st = ctx->stream;
+    const int S = fe->S, CAP = fe->CAP;
+    // one problem per flagged sequence whose record is still in the ring
+    PlacesWork w{};
+    std::vector<int> hq, ht;
+    std::vector<double> hT;
+    for (int s = 0; s < S; s++) {
+        if ((which && !which[s]) || frame_t[s] < 0) continue;
+        int slot = -1;
+        for (int k = 0; k < pl.slots; k++)
+            if (pl.frame[k] == frame_t[s]) slot = k;
+        n_pairs[s] = n_inliers[s] = ok[s] = 0;
+        double T[12];
+        la::rodrigues(rvec + 3 * s, T);  // (before the outputs, which may alias the inputs, are cleared)
+        for (int q = 0; q < 3; q++) T[9 + q] = tvec[3 * s + q];
+        for (int q = 0; q < 3; q++) rvec_out[3 * s + q] = tvec_out[3 * s + q] = 0.0;
+        if (slot < 0) continue;
+        w.seq.push_back(s);
+        w.slot.push_back(slot);
+        hq.push_back(s);
+        ht.push_back(s * pl.slots + slot);
+        hT.insert(hT.end(), T, T + 12);
+    }
+    const int P = (int)w.seq.size();
+    if (P == 0) return SVO_OK;
+    ProjMatch m{};
+    m.grid = proj_grid(fe->W, fe->H);
+    double* d_poses = nullptr;
+    if (!carve_scratch(ctx, kScratchDescribe, [&](Carver& c) {
+            w.q_set = c.take<int>(P);
+            w.t_set = c.take<int>(P);
+            d_poses = c.take<double>(12 * (size_t)P);
+            proj_scratch_layout(c, m.scr, (size_t)P, (size_t)CAP, m.grid);
+            w.pairs = c.take<int>(2 * (size_t)P * CAP);
+            w.n_pairs = c.take<int>(P);
+            w.sel_prob = c.take<int>(P);
+            w.obj = c.take<double>(3 * (size_t)P * CAP);
+            w.img = c.take<float>(2 * (size_t)P * CAP);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "%s: workspace alloc failed", who);
+    rc = places_query_set(fe, st);
+    if (rc) return rc;
+    SVO_HIP(ctx, hipMemcpyAsync(w.q_set, hq.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(w.t_set, ht.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(d_poses, hT.data(), sizeof(double) * 12 * P, hipMemcpyHostToDevice, st));
+    // the points: the records in place (set s * slots + slot of the ring); the keypoints: the query sets
+    m.n_pts = pl.n;
+    m.n_kp = pl.q_n;
+    m.p_stride = m.k_stride = CAP;
+    m.xyz = pl.xyz;
+    m.pdesc = reinterpret_cast<const uint32_t*>(pl.desc);
+    m.kxy = pl.q_xy;
+    m.kdesc = reinterpret_cast<const uint32_t*>(pl.q_desc);
+    m.poses = d_poses;
+    m.p_set = w.t_set;
+    m.k_set = w.q_set;
+    m.fx = cfg.K[0];
+    m.fy = cfg.K[4];
+    m.cx = cfg.K[2];
+    m.cy = cfg.K[5];
+    m.w = fe->W;
+    m.h = fe->H;
+    m.radius = params->radius;
+    m.max_dist = params->max_dist;
+    m.ratio_pct = params->ratio_pct;
+    m.pairs = w.pairs;
+    m.n_pairs = w.n_pairs;
+    SVO_HIP(ctx, launch_proj_bin(m, P, st));
+    SVO_HIP(ctx, launch_proj_match(m, P, CAP, st));  // (the counts live on the device: a full list's grid)
+    SVO_HIP(ctx, launch_proj_pairs(m, P, st));
+    // the solver's inputs of every problem (problem k is its own selection)
+    std::vector<int> iota(P), hn(P, 0);
+    for (int k = 0; k < P; k++) iota[k] = k;
+    SVO_HIP(ctx, hipMemcpyAsync(w.sel_prob, iota.data(), sizeof(int) * P, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, launch_places_gather_pairs(w.pairs, w.n_pairs, w.sel_prob, w.q_set, w.t_set, P, CAP, pl.q_xy, pl.xyz,
+                                            w.obj, w.img, st));
+    SVO_HIP(ctx, hipMemcpyAsync(hn.data(), w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));  // (also: hq, ht, hT and iota have left the host)
+    std::vector<double> obj(3 * (size_t)P * CAP);
+    std::vector<float> img(2 * (size_t)P * CAP);
+    std::vector<int> hp(pairs ? 2 * (size_t)P * CAP : 0);
+    for (int k = 0; k < P; k++) {
+        const size_t n = hn[k], o = (size_t)k * CAP;
+        if (n == 0) continue;
+        SVO_HIP(ctx, hipMemcpyAsync(&obj[3 * o], w.obj + 3 * o, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
+        SVO_HIP(ctx, hipMemcpyAsync(&img[2 * o], w.img + 2 * o, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
+        if (pairs)
+            SVO_HIP(ctx, hipMemcpyAsync(&hp[2 * o], w.pairs + 2 * o, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, st));
+    }
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<int> inl(CAP);
+    for (int k = 0; k < P; k++) {
+        const int s = w.seq[k], n = hn[k];
+        const size_t o = (size_t)k * CAP;
+        n_pairs[s] = n;
+        if (pairs) std::memcpy(pairs + 2 * (size_t)s * cap, &hp[2 * o], sizeof(int) * 2 * std::min(n, cap));
+        if (n < 4) continue;
+        int ni = 0;
+        const int found = svo_solve_pnp_ransac(ctx, &obj[3 * o], &img[2 * o], n, cfg.K, cfg.pnp_iterations,
+                                               cfg.pnp_reproj, cfg.pnp_confidence, rvec_out + 3 * s, tvec_out + 3 * s,
+                                               inl.data(), &ni);
+        if (found < 0) return found;
+        ok[s] = found;
+        n_inliers[s] = found ? ni : 0;
+        if (!found)
+            for (int q = 0; q < 3; q++) rvec_out[3 * s + q] = tvec_out[3 * s + q] = 0.0;
         if (inliers && found) std::memcpy(inliers + (size_t)s * cap, inl.data(), sizeof(int) * std::min(ni, cap));
     }
     return SVO_OK;

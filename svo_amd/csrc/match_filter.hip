@@ -3,6 +3,7 @@
 // hamming_knn2_kernel wrote, integers only, then the kept pairs compacted in
 // ascending query index. The order is part of the result: it decides the draws
 // of the RANSAC that takes the pairs.
+#include "block_compact.hpp"
 #include "orb.hpp"
 
 namespace svo {
@@ -12,9 +13,7 @@ namespace {
 constexpr int kFilterThreads = 256;
 
 // One block per problem. Queries go by in chunks of 256, one per thread: keep is
-// svo_match_filter's rule; a wave's ballot gives each kept query its place among
-// the wave's (the popcount of the lower lanes' bits), the four waves' counts go
-// through LDS for the waves in front, and `base` carries the chunks before.
+// svo_match_filter's rule; block_compact_row places the kept ones in order.
 __global__ void __launch_bounds__(kFilterThreads) match_filter_kernel(
     const int2* __restrict__ idx_qt, const int2* __restrict__ dist_qt, const int2* __restrict__ idx_tq,
     const int* __restrict__ nq_p, const int* __restrict__ nt_p, int q_stride, int t_stride, int ratio_pct,
@@ -24,7 +23,6 @@ __global__ void __launch_bounds__(kFilterThreads) match_filter_kernel(
     const int p = blockIdx.x;
     const int nq = min(nq_p[q_set ? q_set[p] : p], q_stride);
     const int nt = min(nt_p[t_set ? t_set[p] : p], t_stride);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int2* iq = idx_qt + (size_t)p * q_stride;
     const int2* dq = dist_qt + (size_t)p * q_stride;
     const int2* it = idx_tq ? idx_tq + (size_t)p * t_stride : nullptr;
@@ -42,17 +40,8 @@ __global__ void __launch_bounds__(kFilterThreads) match_filter_kernel(
                 keep = i.y >= 0 && (long long)d.x * 100 < (long long)ratio_pct * d.y;
             if (keep && it) keep = it[i1].x == q;
         }
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int before = base, total = base;
-        for (int w = 0; w < kFilterThreads / 64; w++) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
-        if (keep) out[before + __popcll(b & ((1ull << lane) - 1))] = make_int2(q, i1);  // < nq <= q_stride
-        base = total;
-        __syncthreads();  // s_wave is rewritten by the next chunk
+        const int row = block_compact_row<kFilterThreads>(keep, base, s_wave);
+        if (keep) out[row] = make_int2(q, i1);  // < nq <= q_stride
     }
     if (threadIdx.x == 0) n_pairs[p] = base;
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "layout.hpp"
+#include "match_projected.hpp"
 
 using svo::Carver;
 
@@ -125,6 +126,16 @@ int main() {
             }
         }
     });
+    // svo_match_projected's scratch (match_projected.hpp): no keypoint rows, one
+    // problem on the smallest grid, and the largest grid
+    for (int k = 0; k < 3; k++) {
+        const int w = k == 2 ? 1241 : 7, h = k == 2 ? 376 : 5;
+        const size_t problems = k == 0 ? 0 : k == 1 ? 1 : 33, rows = k == 0 ? 0 : k == 1 ? 1 : 2001;
+        check(k == 0 ? "proj scratch: empty" : k == 1 ? "proj scratch: one" : "proj scratch: 33 x 2001", [=](Probe& p) {
+            svo::ProjScratch s;
+            svo::proj_scratch_layout(p, s, problems, rows, svo::proj_grid(w, h));
+        });
+    }
     {  // measured only: 3 << 30 doubles (24 GiB) between two small members must not wrap
         Probe meas;
         meas.take<int>(5);
