@@ -359,6 +359,15 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
                                  uint8_t* status, float* err, int win_w, int win_h,
                                  int max_level, int crit_type, int max_count, double epsilon,
                                  int flags, double min_eig_threshold);
+/* The same call as two launches, points [0, split) and [split, n) (0 <= split <= n;
+ * 0 or n: one launch): a point's result does not depend on the launch it is in, so
+ * the outputs equal svo_calc_optical_flow_pyr_lk's bit for bit (the batched front
+ * end tracks a keyframe's new features in a launch of their own). */
+int svo_calc_optical_flow_pyr_lk_split(svo_ctx* ctx, const svo_image* prev, const svo_image* next,
+                                       const float* prev_xy, int n, int split, float* next_xy,
+                                       uint8_t* status, float* err, int win_w, int win_h,
+                                       int max_level, int crit_type, int max_count,
+                                       double epsilon, int flags, double min_eig_threshold);
 /* Gauss-Newton iterations executed by the last LK call, summed over points and
  * levels (the "LK iters/s" metric numerator). */
 int64_t svo_lk_last_iterations(const svo_ctx* ctx);

@@ -147,6 +147,9 @@ _SIGS = [
     ("svo_calc_optical_flow_pyr_lk", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, _f32p, _u8p, _f32p,
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_double, C.c_int, C.c_double]),
+    ("svo_calc_optical_flow_pyr_lk_split", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, C.c_int, _f32p, _u8p, _f32p,
+                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_double, C.c_int, C.c_double]),
     ("svo_lk_last_iterations", C.c_int64, [_vp]),
     ("svo_stereo_match_rows", C.c_int, [_vp, _vp, _vp, _f32p, C.c_int, _vp, _f32p, _u8p, _i32p, _i32p]),
     ("svo_frontend_set_stereo_matcher", C.c_int, [_vp, _vp]),
@@ -989,8 +992,10 @@ class Context:
     def calc_optical_flow_pyr_lk(self, prev: Image, nxt: Image, prev_pts, next_pts=None,
                                  win_size=(21, 21), max_level: int = 3,
                                  criteria=(TERM_COUNT | TERM_EPS, 30, 0.01), flags: int = 0,
-                                 min_eig_threshold: float = 1e-4, want_err: bool = True):
-        """cv::calcOpticalFlowPyrLK -> (next_pts (n,2) f32, status (n,) u8, err (n,) f32)."""
+                                 min_eig_threshold: float = 1e-4, want_err: bool = True, split: int = None):
+        """cv::calcOpticalFlowPyrLK -> (next_pts (n,2) f32, status (n,) u8, err (n,) f32).
+        split: the call as two launches, points [0, split) and [split, n)
+        (svo_calc_optical_flow_pyr_lk_split); the same outputs."""
         prev_pts = _c(prev_pts, np.float32).reshape(-1, 2)
         n = len(prev_pts)
         if next_pts is None:
@@ -1000,11 +1005,15 @@ class Context:
         status = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32) if want_err else None
         ctype, count, eps = criteria
-        self._check(lib().svo_calc_optical_flow_pyr_lk(
-            self.handle, prev.handle, nxt.handle, _p(prev_pts, _f32p), n, _p(nxt_pts, _f32p),
-            _p(status, _u8p), _p(err, _f32p) if err is not None else None, int(win_size[0]),
-            int(win_size[1]), int(max_level), int(ctype), int(count), float(eps), int(flags),
-            float(min_eig_threshold)))
+        tail = (_p(nxt_pts, _f32p), _p(status, _u8p), _p(err, _f32p) if err is not None else None, int(win_size[0]),
+                int(win_size[1]), int(max_level), int(ctype), int(count), float(eps), int(flags),
+                float(min_eig_threshold))
+        if split is None:
+            self._check(lib().svo_calc_optical_flow_pyr_lk(
+                self.handle, prev.handle, nxt.handle, _p(prev_pts, _f32p), n, *tail))
+        else:
+            self._check(lib().svo_calc_optical_flow_pyr_lk_split(
+                self.handle, prev.handle, nxt.handle, _p(prev_pts, _f32p), n, int(split), *tail))
         return nxt_pts, status, err
 
     def lk_last_iterations(self) -> int:

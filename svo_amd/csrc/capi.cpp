@@ -470,11 +470,11 @@ int svo_bucket_features(svo_ctx* ctx, const float* xy, const int* ages, int n, i
 }
 
 // ------------------------------------------------------------------ LK
-int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_image* next,
-                                 const float* prev_xy, int n, float* next_xy, uint8_t* status,
-                                 float* err, int win_w, int win_h, int max_level, int crit_type,
-                                 int max_count, double epsilon, int flags,
-                                 double min_eig_threshold) {
+// split in (0, n): two launches, points [0, split) and -- through LKBatch::first --
+// [split, n); otherwise one over [0, n)
+static int lk_call(svo_ctx* ctx, const svo_image* prev, const svo_image* next, const float* prev_xy, int n,
+                   float* next_xy, uint8_t* status, float* err, int win_w, int win_h, int max_level, int crit_type,
+                   int max_count, double epsilon, int flags, double min_eig_threshold, int split) {
     if (!ctx || !prev || !next) return SVO_ERR_ARG;
     ctx->lk_iters = 0;
     if (n == 0) return SVO_OK;  // OpenCV releases the outputs and returns
@@ -515,7 +515,7 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
     Staged* ds;
     char* dbase;
     float *dprev, *dnext, *derr;
-    int* diters;
+    int *diters, *dfirst;
     uint8_t* dst;
     if (!carve_scratch(ctx, kScratchTrack, [&](Carver& c) {
             ds = c.take<Staged>(1);
@@ -524,6 +524,7 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
             dnext = c.take<float>(2 * (size_t)n);
             derr = c.take<float>(n);
             diters = c.take<int>(n);
+            dfirst = c.take<int>(1);
             dst = c.take<uint8_t>(n);
         }))
         return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
@@ -543,7 +544,16 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
     SVO_HIP(ctx, hipMemsetAsync(dbase, 0, dbytes, ctx->stream));  // the zero borders
     SVO_HIP(ctx, launch_scharr(ds->pd, &ds->dd, 1, prev->w, prev->h, ml + 1, ctx->stream));
     LKBatch b{ds->pd, ds->pd + 1, &ds->dd, dprev, dnext, dst, err ? derr : nullptr, diters, nullptr, n, n};
-    SVO_HIP(ctx, launch_lk(b, 1, n, p, ctx->stream));
+    if (split > 0 && split < n) {
+        SVO_HIP(ctx, hipMemcpyAsync(dfirst, &split, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        LKBatch head = b;
+        head.n = split;
+        SVO_HIP(ctx, launch_lk(head, 1, split, p, ctx->stream));
+        b.first = dfirst;
+        SVO_HIP(ctx, launch_lk(b, 1, n - split, p, ctx->stream));
+    } else {
+        SVO_HIP(ctx, launch_lk(b, 1, n, p, ctx->stream));
+    }
     std::vector<int> it(n);
     SVO_HIP(ctx, hipMemcpyAsync(next_xy, dnext, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -554,6 +564,25 @@ int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_
     for (int v : it) s += v;
     ctx->lk_iters = s;
     return SVO_OK;
+}
+
+int svo_calc_optical_flow_pyr_lk(svo_ctx* ctx, const svo_image* prev, const svo_image* next,
+                                 const float* prev_xy, int n, float* next_xy, uint8_t* status,
+                                 float* err, int win_w, int win_h, int max_level, int crit_type,
+                                 int max_count, double epsilon, int flags,
+                                 double min_eig_threshold) {
+    return lk_call(ctx, prev, next, prev_xy, n, next_xy, status, err, win_w, win_h, max_level, crit_type, max_count,
+                   epsilon, flags, min_eig_threshold, 0);
+}
+
+int svo_calc_optical_flow_pyr_lk_split(svo_ctx* ctx, const svo_image* prev, const svo_image* next,
+                                       const float* prev_xy, int n, int split, float* next_xy, uint8_t* status,
+                                       float* err, int win_w, int win_h, int max_level, int crit_type,
+                                       int max_count, double epsilon, int flags, double min_eig_threshold) {
+    if (ctx && (split < 0 || split > n))
+        return set_error(ctx, SVO_ERR_ARG, "svo_calc_optical_flow_pyr_lk_split: split outside 0..n");
+    return lk_call(ctx, prev, next, prev_xy, n, next_xy, status, err, win_w, win_h, max_level, crit_type, max_count,
+                   epsilon, flags, min_eig_threshold, split);
 }
 
 int64_t svo_lk_last_iterations(const svo_ctx* ctx) { return ctx ? ctx->lk_iters : 0; }

@@ -286,6 +286,11 @@ struct LKBatch {
     // sequence; waves loop over any beyond it (a device-side count the host only
     // bounds loosely, e.g. the speculative stereo candidates)
     int grid_hint = 0;
+    // nullable, [nseq] device: the launch covers points [first[s], n_s) of sequence s
+    // (the grid's feature j is point first[s] + j; max_n bounds n_s - first[s]). A
+    // point's result does not depend on the launch it is in, so launches over [0, k)
+    // and [k, n) give what one over [0, n) gives.
+    const int* first = nullptr;
 };
 hipError_t launch_lk(const LKBatch& b, int nseq, int max_n, const LKParams& p, hipStream_t st);
 bool lk_supported(int win_w, int win_h);

@@ -26,6 +26,12 @@ constexpr int kFeBlock = 256;
 // wave per SIMD) it starts at once (36 us in the step, 833.6 vs 874 us step
 // period in the same trace); the usual ~50-100 candidates still take one pass.
 constexpr int kAppendBlock = 256;
+// The deferred keyframe's append runs beside the next temporal LK, which leaves a
+// SIMD room for one more wave but no CU room for four at once: as a 256-thread
+// block it waited 243 us in a 413 us LK (profiles/deferred_keyframe_ab.txt); one
+// wave per sequence starts at once, and the take (tens of candidates) is a pass or
+// two of 64. The same compaction in the same order at either size.
+constexpr int kAppendLoneBlock = 64;
 // post_lk: its chain of dependent passes (compaction chunks, map-point gathers)
 // is latency-bound; 512 threads halve the chunks of a 2000-feature sequence
 // against 256 and still fit beside FAST's 256-thread blocks
@@ -371,6 +377,7 @@ __device__ __forceinline__ void tail_body(const TailBatch& T, int s, bool copy_c
     }
     if (threadIdx.x == 0) {
         T.n_out[s] = n;
+        if (T.n_main) T.n_main[s] = n;
         T.st_n[s] = take;
         if (T.h_over) T.h_over[s] = max(T.cand_n[s] - take, 0);
     }
@@ -623,8 +630,11 @@ hipError_t launch_tail(const TailBatch& tb, int nseq, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st) {
-    hipLaunchKernelGGL(append_kernel<kAppendBlock>, dim3(nseq), dim3(kAppendBlock), 0, st, b);
+hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st, bool lone_wave) {
+    if (lone_wave)
+        hipLaunchKernelGGL(append_kernel<kAppendLoneBlock>, dim3(nseq), dim3(kAppendLoneBlock), 0, st, b);
+    else
+        hipLaunchKernelGGL(append_kernel<kAppendBlock>, dim3(nseq), dim3(kAppendBlock), 0, st, b);
     return hipGetLastError();
 }
 

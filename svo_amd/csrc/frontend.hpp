@@ -93,6 +93,9 @@ struct TailBatch {
     // nullable: [s], incremented when the keyframe reclaims the sequence's map
     // (the observation window's slots remember the epoch of their ids)
     int* map_epoch = nullptr;
+    // nullable: [s], the kept count once more (n_out's value). The deferred
+    // keyframe's next temporal LK reads it while the append already rewrites n_out.
+    int* n_main = nullptr;
 };
 hipError_t launch_tail(const TailBatch& tb, int nseq, hipStream_t st);
 
@@ -124,7 +127,9 @@ struct AppendBatch {
     const float* st_next;
     float* ur;
 };
-hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st);
+// lone_wave: one 64-lane wave per sequence instead of a 256-thread block (an append
+// queued beside a running LK, which leaves no CU room for four waves at once)
+hipError_t launch_append(const AppendBatch& b, int nseq, hipStream_t st, bool lone_wave = false);
 
 // Speculative stereo input, one block per sequence, queued as soon as the step's
 // tracked count n_tracked (post-LK) and the FAST candidates are known, i.e. before

@@ -139,6 +139,47 @@ static StereoTriBatch fe_tri_batch(svo_frontend* fe, const int* counts) {
     return tb;
 }
 
+// append_kernel's inputs: the take's matches (st_next / st_status / st_X of
+// st_xy[0, st_n[s])) behind the kept features xyA / midA / nA
+static AppendBatch fe_append_batch(svo_frontend* fe) {
+    AppendBatch ab;
+    ab.n = fe->nA;
+    ab.xy = fe->xyA;
+    ab.mid = fe->midA;
+    ab.cap = fe->CAP;
+    ab.st_xy = fe->st_xy;
+    ab.st_n = fe->st_n;
+    ab.map = fe->map;
+    ab.map_n = fe->map_n;
+    ab.map_cap = fe->MAPCAP;
+    ab.pend0 = fe->pend0;
+    ab.pend_n = fe->pend_n;
+    ab.added = fe->added;
+    ab.h_n = fe->h_nA;
+    ab.h_added = fe->h_added;
+    ab.st_X = fe->st_X;
+    ab.st_next = fe->st_next;
+    ab.ur = fe->win.ur_feat;  // (null without a stereo window)
+    return ab;
+}
+
+// The keyframe's second half on stream st, behind tail_kernel: the stereo LK of
+// exactly the take (st_n, bounded by max_take), the take's filter + DLT (the same
+// kernel as behind the speculative stereo LK), then the append compacts. beside_lk:
+// the stream runs beside a temporal LK (the deferred keyframe): the append as one
+// wave per sequence.
+int fe_keyframe_append(svo_frontend* fe, int t, int max_take, hipStream_t st, bool beside_lk) {
+    svo_ctx* ctx = fe->ctx;
+    int slot;
+    int rc = fe_stereo_lk(fe, t, fe->st_n, max_take, st);
+    if (rc) return rc;
+    SVO_HIP(ctx, launch_stereo_tri(fe_tri_batch(fe, fe->st_n), fe->S, max_take, st));
+    ph_begin(fe, PH_APPEND, st, &slot);
+    SVO_HIP(ctx, launch_append(fe_append_batch(fe), fe->S, st, beside_lk));
+    ph_end(fe, st, slot);
+    return SVO_OK;
+}
+
 // The keyframe of every sequence on stream st (R:src/tracking.cpp:247-255):
 // outlier compaction (inlier bits `bits`, or every point when n_in is all zero)
 // + the first candidates up to the sequence's target (h_target: n_features on a
@@ -150,9 +191,11 @@ static StereoTriBatch fe_tri_batch(svo_frontend* fe, const int* counts) {
 // SQPnP statistics of these inliers (the bits, the points of that step parity)
 // into h_stats. spec: the speculative stereo LK (fe_queue_spec) already matched
 // every sequence's take candidates: compaction, filter, triangulation and append
-// run as one kernel.
+// run as one kernel. defer (the deferred keyframe):
+// tail_kernel only, which also leaves the kept counts in n_main; the caller
+// queues fe_keyframe_append on another stream behind it.
 int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, const float* xy_in, const int* mid_in,
-                int max_take, hipStream_t st, int stats_parity, bool spec) {
+                int max_take, hipStream_t st, int stats_parity, bool spec, bool defer) {
     svo_ctx* ctx = fe->ctx;
     const svo_frontend_config& c = fe->cfg;
     int slot;
@@ -179,6 +222,7 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
     tb.st_n = fe->st_n;
     tb.h_over = fe->h_over;
     tb.map_epoch = fe->win.ring.map_epoch;  // (null without a window)
+    if (defer) tb.n_main = fe->n_main;
     if (stats_parity >= 0) {
         tb.stats_obj = fe->obj_b[stats_parity];
         tb.stats_out = fe->h_stats;
@@ -187,42 +231,16 @@ int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, 
         tb.cx = c.K[2];
         tb.cy = c.K[5];
     }
-    AppendBatch ab;
-    ab.n = fe->nA;
-    ab.xy = fe->xyA;
-    ab.mid = fe->midA;
-    ab.cap = fe->CAP;
-    ab.st_xy = fe->st_xy;
-    ab.st_n = fe->st_n;
-    ab.map = fe->map;
-    ab.map_n = fe->map_n;
-    ab.map_cap = fe->MAPCAP;
-    ab.pend0 = fe->pend0;
-    ab.pend_n = fe->pend_n;
-    ab.added = fe->added;
-    ab.h_n = fe->h_nA;
-    ab.h_added = fe->h_added;
-    ab.st_X = fe->st_X;
-    ab.st_next = fe->st_next;
-    ab.ur = fe->win.ur_feat;  // (null without a stereo window)
     if (spec) {
         ph_begin(fe, PH_TAIL, st, &slot);
-        SVO_HIP(ctx, launch_keyframe_fused(tb, ab, fe->S, st));
+        SVO_HIP(ctx, launch_keyframe_fused(tb, fe_append_batch(fe), fe->S, st));
         ph_end(fe, st, slot);
         return SVO_OK;
     }
     ph_begin(fe, PH_TAIL, st, &slot);
     SVO_HIP(ctx, launch_tail(tb, fe->S, st));
     ph_end(fe, st, slot);
-    int rc = fe_stereo_lk(fe, t, fe->st_n, max_take, st);
-    if (rc) return rc;
-    // the take's filter + DLT (the same kernel as behind the speculative stereo
-    // LK), then the append compacts
-    SVO_HIP(ctx, launch_stereo_tri(fe_tri_batch(fe, fe->st_n), fe->S, max_take, st));
-    ph_begin(fe, PH_APPEND, st, &slot);
-    SVO_HIP(ctx, launch_append(ab, fe->S, st));
-    ph_end(fe, st, slot);
-    return SVO_OK;
+    return defer ? SVO_OK : fe_keyframe_append(fe, t, max_take, st, false);
 }
 
 // The speculative stereo LK of step t (StereoPrepBatch) on the FAST stream,
@@ -590,17 +608,35 @@ int fe_front_lk(svo_frontend* fe, int t) {
         const LKParams lp = fe_temporal_params(fe);
         const PyrDesc* dprev = fe->d_desc + (size_t)((t - 1) % fe->T) * S;
         hipStream_t sl = fe->st_lk;
+        // behind a deferred keyframe: the kept features [0, n_main) here -- not nA,
+        // which the append rewrites while this launch is still starting waves --
+        // and the new ones in a launch of their own behind the append (below)
+        const bool split = fe->ahead.split_lk;
         SVO_HIP(ctx, hipStreamWaitEvent(sl, fe->ev_pyr, 0));
         LKBatch lb{dprev, dcur, fe->d_der + (size_t)((t - 1) % 3) * S, fe->xyA, fe->next_xy, fe->status, nullptr,
-                   fe->iters, fe->nA, 0, fe->CAP};
+                   fe->iters, split ? fe->n_main : fe->nA, 0, fe->CAP};
         ph_begin(fe, PH_LK, sl, &slot);
         // grid bound CAP: the host counts of the previous keyframe may not be back yet
         SVO_HIP(ctx, launch_lk(lb, S, fe->CAP, lp, sl));
         ph_end(fe, sl, slot);
         SVO_HIP(ctx, hipEventRecord(fe->ev_lk, sl));
+        if (split) {
+            // the new features [n_main, nA) on the FAST stream, behind the append that
+            // made them, beside the launch above: same parameters, same output arrays
+            // (disjoint points). The post-LK, behind both on the LK stream, waits here.
+            hipStream_t sf = fe->st_fast;
+            SVO_HIP(ctx, hipStreamWaitEvent(sf, fe->ev_pyr, 0));
+            LKBatch l2 = lb;
+            l2.counts = fe->nA;
+            l2.first = fe->n_main;
+            SVO_HIP(ctx, launch_lk(l2, S, std::min(std::max(fe->ahead.split_max, 0), fe->CAP), lp, sf));
+            SVO_HIP(ctx, hipEventRecord(fe->ev_lk2, sf));
+            SVO_HIP(ctx, hipStreamWaitEvent(sl, fe->ev_lk2, 0));
+        }
         // frame t-1's images are not read after this LK (its stereo LK and keyframe
-        // ran before it on this stream or were waited for there): its ring slot may
-        // be streamed into once this event fires
+        // ran before it on this stream or were waited for there; a deferred
+        // keyframe's stereo LK and the second launch: the wait above): its ring
+        // slot may be streamed into once this event fires
         if (!fe->up.ev_free.empty()) {
             const int fs = (t - 1) % fe->T;
             SVO_HIP(ctx, hipEventRecord(fe->up.ev_free[fs], sl));

@@ -30,6 +30,18 @@ FeSwitches fe_read_switches(const svo_frontend_config& c) {
     sw.debug = is("SVO_FE_DEBUG", '1');
     sw.pool_pin = env("SVO_POOL_PIN") ? (is("SVO_POOL_PIN", '1') ? 1 : 0) : -1;
     sw.pool_spin_us = pool_spin_env();
+    // the deferred keyframe: SVO_FE_DEFER_KF=1 / 0, or by default where the batch is
+    // large enough (kDeferMinFeatures) unless a switch of the speculative schedule is
+    // set (they keep meaning what they meant); it speculates nothing
+    if (c.keyframe_rule == SVO_KF_EVERY && !c.use_orb)
+        sw.defer_kf = env("SVO_FE_DEFER_KF")
+                          ? is("SVO_FE_DEFER_KF", '1')
+                          : !env("SVO_FE_SPEC_MARGIN") && !env("SVO_FE_SPEC_EARLY") &&
+                                (long long)c.n_seq * c.n_features >= kDeferMinFeatures;
+    if (sw.defer_kf) {
+        sw.spec_margin = -1;
+        sw.spec_early = 0;
+    }
     if (c.use_orb) {  // ORB: detection at the keyframe, the serial keyframe path
         sw.fast_pre = 0;
         sw.spec_margin = -1;
@@ -130,6 +142,7 @@ int create_device_state(svo_frontend* fe) {
         fe->pend0 = p.take<int>(S);
         fe->pend_n = p.take<int>(S);
         fe->spec_n = p.take<int>(S);
+        fe->n_main = p.take<int>(S);
         fe->kps = p.take<float>(3 * (size_t)S * fe->KCAP);
         fe->cand = p.take<float>(2 * (size_t)S * fe->BCAP);
         fe->midA = p.take<int>((size_t)S * CAP);
@@ -323,7 +336,7 @@ int create_streams_and_events(svo_frontend* fe) {
     fe->st_copy = ctx->fe_copy;
     for (hipEvent_t* e : {&fe->ev_pyr, &fe->ev_fast, &fe->ev_lk, &fe->ev_post, &fe->ev_tail, &fe->ev_stats,
                           &fe->ev_pyr_r_b[0], &fe->ev_pyr_r_b[1], &fe->ev_pre, &fe->ev_fdone, &fe->ev_full_b[0],
-                          &fe->ev_full_b[1]})
+                          &fe->ev_full_b[1], &fe->ev_app, &fe->ev_lk2})
         (void)hipEventCreateWithFlags(e, hipEventDisableTiming);
     fe->ev_full = fe->ev_full_b[0];
     SVO_HIP(ctx, hipMemcpyAsync(fe->d_desc, fe->desc_host.data(), sizeof(PyrDesc) * fe->desc_host.size(),
@@ -449,7 +462,8 @@ void svo_frontend_destroy(svo_frontend* fe) {
     for (auto& e : fe->ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {fe->ev_pyr, fe->ev_fast, fe->ev_lk, fe->ev_post, fe->ev_tail, fe->ev_stats, fe->ev_pyr_r_b[0],
-                         fe->ev_pyr_r_b[1], fe->ev_pre, fe->ev_fdone, fe->ev_full_b[0], fe->ev_full_b[1]})
+                         fe->ev_pyr_r_b[1], fe->ev_pre, fe->ev_fdone, fe->ev_full_b[0], fe->ev_full_b[1], fe->ev_app,
+                         fe->ev_lk2})
         if (e) (void)hipEventDestroy(e);
     if (fe->score_map) (void)hipFree(fe->score_map);
     for (hipEvent_t e : fe->up.ev)

@@ -23,6 +23,14 @@ constexpr int kEvRing = 256;  // phase-timing events (pairs)
 // rounds measured 2-6 % slower on the KITTI bench
 constexpr int kChunk0 = 2;
 
+// The deferred keyframe pays where the next temporal LK is long enough to hide the
+// stereo LK -> append -> second LK chain beside it (~0.2 ms of latency): n_seq x
+// n_features from here on. Measured at 2,000 features (profiles/deferred_keyframe_ab.txt):
+// 64 sequences +3.4 % (LK 0.42 ms), 256 sequences +2 % to +2.7 % (LK 1.68 ms); at 16
+// sequences (LK 0.15 ms) the chain is the longer of the two and a first form of this
+// schedule measured 2-10 % slower, so small batches keep the speculative schedule.
+constexpr long long kDeferMinFeatures = 128000;
+
 // Everything read from the environment, once, when a front end is created
 // (fe_read_switches).
 struct FeSwitches {
@@ -40,6 +48,14 @@ struct FeSwitches {
     // speculative stereo LK of step t goes out in its first half, behind FAST(t),
     // sized from the features before LK (nA) with margin spec_margin + lk_loss
     int spec_early = 1;
+    // the deferred keyframe (SVO_KF_EVERY with FAST only): behind
+    // RANSAC only tail_kernel runs ahead of the next temporal LK; the stereo LK of
+    // exactly the take, the append and a second LK launch over the new features run
+    // beside that LK, and nothing is speculated (spec_margin -1, spec_early 0).
+    // SVO_FE_DEFER_KF=1 selects it, 0 the speculative schedule; unset, it is the
+    // default for batches of kDeferMinFeatures and more, unless SVO_FE_SPEC_MARGIN or
+    // SVO_FE_SPEC_EARLY is set explicitly (the speculative schedule then).
+    bool defer_kf = false;
     bool trace = false;  // SVO_FE_TRACE=1: the host-side step trace (FeTrace)
     // final SQPnP fits on the device (SVO_FE_DEVICE_FITS=1) instead of the host pool
     // (launch_sqpnp_fit: the eigen-decomposition, the SQP runs over waves, the
@@ -55,7 +71,7 @@ struct FeSwitches {
     double pool_spin_us = 400.0;  // SVO_POOL_SPIN_US (Pool)
 };
 // (ORB -- detection at the keyframe, the serial keyframe path -- overrides
-// fast_pre = 0, spec_margin = -1, spec_early = 0)
+// fast_pre = 0, spec_margin = -1, spec_early = 0, defer_kf = false)
 FeSwitches fe_read_switches(const svo_frontend_config& c);
 
 // What is queued or built ahead of the step that will use it. A frame index
@@ -78,6 +94,12 @@ struct FeAhead {
     bool fits_pending = false;  // the final pose fits of the last step; the step's tail -> fe_finish_fits
     int fit_parity = 0;         // step parity whose RANSAC results they refine
     bool full_queued = false;   // this step's full D2H copy is queued; fe_queue_full, reset by fe_front_lk
+    // the last keyframe was deferred: n_main holds its kept counts and its append
+    // runs on the FAST stream, so the next temporal LK goes out as two launches,
+    // [0, n_main) on the LK stream and [n_main, nA) behind the append; the step's
+    // tail -> fe_front_lk (init's keyframe is serial: one launch over [0, nA))
+    bool split_lk = false;
+    int split_max = 0;          // host bound of nA - n_main (the deferred keyframe's max_take)
     int stepped = -1;           // last completed step (init: t0), -1 before init; step / init -> queue_frames' window
     // everything: init, a restart of the ring
     void forget_all() { *this = FeAhead{}; }
@@ -217,6 +239,7 @@ struct svo_frontend {
     int* st_n;
     int *pend0, *pend_n;  // PendingMap ranges
     int* spec_n;          // speculative stereo candidates per sequence (StereoPrepBatch)
+    int* n_main;          // the deferred keyframe's kept counts (TailBatch::n_main)
     float *kps, *cand;
     int *midA, *midB, *iters, *nA, *kn, *bn, *map_n, *added, *rowcnt, *scr;
     uint8_t* status;
@@ -282,6 +305,9 @@ struct svo_frontend {
     hipEvent_t ev_pyr = nullptr;    // left pyramid of the step's frame built
     hipEvent_t ev_fast = nullptr;   // FAST (and the speculative stereo LK behind it) done
     hipEvent_t ev_lk = nullptr, ev_post = nullptr, ev_tail = nullptr;
+    // the deferred keyframe (FAST stream): its append done; the second temporal LK
+    // launch (the new features) behind it done
+    hipEvent_t ev_app = nullptr, ev_lk2 = nullptr;
     hipEvent_t ev_stats = nullptr;  // SQPnP statistics + final fits of the last step done (copy stream)
     hipEvent_t ev_pyr_r_b[2] = {nullptr, nullptr};  // right pyramid of frame f built: [f & 1]
     hipEvent_t ev_pre = nullptr;    // the pre-detection ahead.pre_t done (context stream)
@@ -340,7 +366,8 @@ int fe_fast_and_bucket(svo_frontend* fe, const PyrDesc* descs_cur, bool use_mask
                        bool prebinned = false, int stage = kFastAll);
 int fe_orb_detect(svo_frontend* fe, int t, bool use_mask, hipStream_t st);
 int fe_keyframe(svo_frontend* fe, int t, const int* n_in, const uint32_t* bits, const float* xy_in, const int* mid_in,
-                int max_take, hipStream_t st, int stats_parity, bool spec = false);
+                int max_take, hipStream_t st, int stats_parity, bool spec = false, bool defer = false);
+int fe_keyframe_append(svo_frontend* fe, int t, int max_take, hipStream_t st, bool beside_lk);
 PendingMap fe_pending(svo_frontend* fe);
 void fe_set_pose(svo_frontend* fe, int s, bool ok, const double rvec[3], const double tvec[3]);
 int fe_window_record(svo_frontend* fe, int t, hipStream_t st);

@@ -13,6 +13,9 @@
 //     drop outliers + the keyframe's first corners       [fe_kernels]    :218-229
 //     stereo LK of those corners into right frame t      [lk_multi.hip]  findLeftFeaturesInRight :94-118
 //     |yR - yL| < 40, DLT triangulation, z > 0, append   [fe_kernels]    triangulateNewMapPoints :120-152
+//       (deferred, the default of large batches: these two beside the next step's
+//        temporal LK of the kept features, and a second LK launch over the new ones
+//        behind them)
 //     (window enabled) the frame's lists into its ring slot [fe_kernels]  the back end's input, DESIGN.md §10
 //
 // Which frames are keyframes: every frame, topping the set up to n_features
@@ -26,7 +29,8 @@
 //
 // Streams (the box gives a process 4 hardware queues, GPU_MAX_HW_QUEUES): the
 // LK stream (LK, post-LK, scoring, keyframe; highest priority), the FAST stream
-// (box binning, FAST, speculative stereo LK; lowest), the context stream
+// (box binning, FAST, the deferred keyframe's stereo LK + append + second LK
+// launch, or the speculative stereo LK; lowest), the context stream
 // (pyramids, FAST pre-detection) and the copy stream (host copies, SQPnP
 // statistics).
 //
@@ -387,8 +391,12 @@ int step_keyframe_and_next(svo_frontend* fe, int t, FeStep& st) {
     SVO_HIP(ctx, hipStreamWaitEvent(sl, fe->ev_fast, 0));
     // drop the outliers (the kernel reads the inlier bits from host-coherent
     // memory), then the keyframe: candidates, stereo LK, triangulation, append
+    // (deferred: the compaction and the candidates only; the rest below, on the
+    // FAST stream)
+    const bool defer = fe->sw.defer_kf;
     const auto tkq = fe_clock::now();
-    rc = fe_keyframe(fe, t, fe->nB, fe->h_best, fe->xyB, fe->midB, st.max_take, sl, fe->ahead.stats_parity, st.spec_ok);
+    rc = fe_keyframe(fe, t, fe->nB, fe->h_best, fe->xyB, fe->midB, st.max_take, sl, fe->ahead.stats_parity, st.spec_ok,
+                     defer);
     if (rc) return rc;
     SVO_HIP(ctx, hipEventRecord(fe->ev_tail, sl));
     // (fe_keyframe took the statistics: done with the compaction)
@@ -413,14 +421,34 @@ int step_keyframe_and_next(svo_frontend* fe, int t, FeStep& st) {
     // keyframe; only the SQPnP statistics of these inliers go to the GPU ahead of
     // it (the pose fits need them at the next step's start).
     SVO_HIP(ctx, hipStreamWaitEvent(sf, fe->ev_tail, 0));
-    // the window's copy of this frame's lists, on the FAST stream behind the
-    // keyframe: the next keyframe, which rewrites them, waits for that stream's
-    // FAST chain (ev_fast) queued behind this copy
-    rc = fe_window_record(fe, t, sf);
-    if (rc) return rc;
-    // the place memory's record of this frame, behind it on the same terms
-    rc = fe_places_record(fe, t, sf);
-    if (rc) return rc;
+    if (defer) {
+        // the deferred keyframe's second half: the stereo LK of exactly the take, the
+        // triangulation and the append on the FAST stream, beside the next step's LK
+        // of the kept features. Whatever reads this frame's final lists is on this
+        // stream behind it (the records and the box binning below) or waits for
+        // ev_app (the host, at the end of this step); the next step's LK of the new
+        // features follows it here (fe_front_lk).
+        rc = fe_keyframe_append(fe, t, st.max_take, sf, true);
+        if (rc) return rc;
+        SVO_HIP(ctx, hipEventRecord(fe->ev_app, sf));
+        fe->ahead.split_lk = true;
+        fe->ahead.split_max = st.max_take;
+        st.TP("append queued");
+    }
+    const auto records = [&]() -> int {
+        // the window's copy of this frame's lists, on the FAST stream behind the
+        // keyframe: the next keyframe, which rewrites them, waits for that stream's
+        // FAST chain (ev_fast) queued behind this copy
+        int rr = fe_window_record(fe, t, sf);
+        if (rr) return rr;
+        // the place memory's record of this frame, behind it on the same terms
+        return fe_places_record(fe, t, sf);
+    };
+    // (deferred: behind the next step's second LK launch, which the post-LK waits for)
+    if (!defer) {
+        rc = records();
+        if (rc) return rc;
+    }
     // this step's counts, before the next step's first half re-fills the mirrors
     for (int s = 0; s < S; s++) {
         st.lk_its += fe->h_itsum[s];
@@ -440,6 +468,10 @@ int step_keyframe_and_next(svo_frontend* fe, int t, FeStep& st) {
         rc = fe_front_lk(fe, t + 1);
         if (rc) return rc;
     }
+    if (defer) {
+        rc = records();
+        if (rc) return rc;
+    }
     SVO_HIP(ctx, launch_box_bin(fe_fast_batch(fe, dcur, true), S, fe->W, fe->H, sf));
     fe->ahead.boxes_binned = true;
     if (next_ok) {
@@ -450,9 +482,10 @@ int step_keyframe_and_next(svo_frontend* fe, int t, FeStep& st) {
     st.TP("next front queued");
     st.ms_enqueue += fe_ms_since(tkq);
     // wait for this step's keyframe only (the statistics, the next frame's
-    // pyramid and the prefetched first half keep running into the next step)
+    // pyramid and the prefetched first half keep running into the next step);
+    // deferred: for its append, beside the next step's LK
     const auto tw = fe_clock::now();
-    SVO_HIP(ctx, hipEventSynchronize(fe->ev_tail));
+    SVO_HIP(ctx, hipEventSynchronize(defer ? fe->ev_app : fe->ev_tail));
     st.ms_wait_kf = fe_ms_since(tw);
     st.TP("synced");
     return SVO_OK;
@@ -482,7 +515,8 @@ void step_fill_stats(const svo_frontend* fe, const FeStep& st, svo_frontend_stat
     int64_t mh = 0;
     for (int s = 0; s < S; s++) mh = std::max<int64_t>(mh, fe->rs[s].nh);
     stats->max_hypotheses = mh;
-    stats->serial_keyframe = st.spec_ok ? 0 : 1;
+    // (the deferred keyframe is neither: nothing speculated, nothing to fall back from)
+    stats->serial_keyframe = fe->sw.defer_kf || st.spec_ok ? 0 : 1;
     stats->full_copy = st.have_full ? 1 : 0;
     // Tracking::nextFrame's rule: a keyframe takes every masked corner, so a
     // corner left out for lack of capacity (n_features) is a deviation

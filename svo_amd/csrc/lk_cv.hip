@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void lk_cv_kernel(LKBatch B, LKDev p, CvOrder c
     const int lane = threadIdx.x;
     const int seq = blockIdx.y;
     const int n = B.counts ? B.counts[seq] : B.n;
-    const int pt = blockIdx.x;
+    const int pt = lk_first(B, seq) + blockIdx.x;
     if (pt >= n) return;
     const size_t base = (size_t)seq * B.cap;
     const float* __restrict__ prev_xy = B.prev_xy + 2 * base;

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64) void lk_cvq_kernel(LKBatch B, LKDev p) {
     const XcdTile tile = xcd_tile();  // (blocks in XCD order, as lk_multi_kernel)
     const int seq = tile.y;
     const int n = B.counts ? B.counts[seq] : B.n;
-    const int pt0 = tile.x * FPW;
+    const int pt0 = lk_first(B, seq) + tile.x * FPW;
     if (pt0 >= n) return;
     const int pt = pt0 + g;
     const bool live = pt < n;

@@ -91,6 +91,9 @@ __device__ __forceinline__ float uni_f(float v) {
 }
 __device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// the first point of sequence seq a launch covers (LKBatch::first; 0 without it)
+__device__ __forceinline__ int lk_first(const LKBatch& B, int seq) { return B.first ? B.first[seq] : 0; }
+
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();

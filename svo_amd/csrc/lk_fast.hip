@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void lk_fast_kernel(LKBatch B, LKDev p) {
     const int seq = blockIdx.y;
     const int n = B.counts ? B.counts[seq] : B.n;
     // a wave per feature; a grid smaller than the count (LKBatch::grid_hint) loops
-    for (int pt = blockIdx.x * 4 + wid; pt < n; pt += gridDim.x * 4) {
+    for (int pt = lk_first(B, seq) + blockIdx.x * 4 + wid; pt < n; pt += gridDim.x * 4) {
     const size_t base = (size_t)seq * B.cap;
     const float* __restrict__ prev_xy = B.prev_xy + 2 * base;
     float* __restrict__ next_xy = B.next_xy + 2 * base;

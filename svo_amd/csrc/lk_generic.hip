@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void lk_kernel(LKBatch B, LKDev p) {
     const int wid = threadIdx.x >> 6;
     const int seq = blockIdx.y;
     const int n = B.counts ? B.counts[seq] : B.n;
-    const int pt = blockIdx.x * 4 + wid;
+    const int pt = lk_first(B, seq) + blockIdx.x * 4 + wid;
     if (pt >= n) return;
     const size_t base = (size_t)seq * B.cap;
     const float* __restrict__ prev_xy = B.prev_xy + 2 * base;

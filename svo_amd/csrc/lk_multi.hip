@@ -209,9 +209,10 @@ __global__ __launch_bounds__(64, MINW) void lk_multi_kernel(LKBatch B, LKDev p) 
     const XcdTile tile = xcd_tile();
     const int seq = tile.y;
     const int n = B.counts ? B.counts[seq] : B.n;
+    const int first = lk_first(B, seq);
     int tx = tile.x;
 next_tile:  // (LOOP: the block's next tile, gridDim.x further on)
-    const int pt0 = tx * FPW;
+    const int pt0 = first + tx * FPW;
     if (pt0 >= n) return;
     const int pt = pt0 + g;
     const bool live = pt < n;

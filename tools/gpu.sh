@@ -11,7 +11,8 @@
 #   pmc TAG CONFIG [SEQ]    FETCH_SIZE / WRITE_SIZE passes of a bench run of CONFIG,
 #                           folded into profiles/pmc_summary.json (configs[CONFIG])
 #   mix TAG [BENCH_ARGS]    SQ instruction mix per wave of every step kernel
-#                           (mix TAG --cmd CMD..: of any command's kernels)
+#                           (mix TAG --cmd CMD..: of any command's kernels; MIX_EACH=REGEX: also
+#                           every dispatch of the kernels whose name matches, in dispatch order)
 #   lksplit                 LK VALU / time with the iteration cap at 1, 2, 50
 #   lkab "V1 V2 .."         standalone LK kernel time per SVO_LK_VARIANT (or $LKAB_VAR) value
 #   lkmem [LIB ..]          LK memory-pipeline + issue counters (TA, TCP, SQ), per library build
@@ -107,8 +108,10 @@ run_mix() {
         -- $B >> $O/mix.log 2>&1 || fail mix2 $O/mix.log
     MIX_CMD="$B" MIX_JSON=$O/valu_$tag.json python - > $O/mix_$tag.txt <<'P'
 import csv, glob, collections, re
+import json, os
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 disp = collections.defaultdict(set)
+each = collections.defaultdict(lambda: collections.defaultdict(float))
 for f in glob.glob('/tmp/ps[12]/**/run_counter_collection.csv', recursive=True):
     for r in csv.DictReader(open(f)):
         m = re.search(r'([a-z_0-9]+_kernel(<[^(]*>)?)', r['Kernel_Name'])
@@ -116,7 +119,8 @@ for f in glob.glob('/tmp/ps[12]/**/run_counter_collection.csv', recursive=True):
         k = m.group(1)
         agg[k][r['Counter_Name']] += float(r['Counter_Value'])
         disp[k].add((f, r['Dispatch_Id']))
-import json, os
+        if os.environ.get("MIX_EACH") and re.search(os.environ["MIX_EACH"], k) and r['Counter_Name'] in ('SQ_INSTS_VALU', 'SQ_WAVES'):
+            each[(k, int(r['Dispatch_Id']))][r['Counter_Name']] += float(r['Counter_Value'])
 summ = {}
 for k, d in agg.items():
     n = len(disp[k]) / 2
@@ -126,6 +130,8 @@ for k, d in agg.items():
                "valu_per_dispatch": round(d.get('SQ_INSTS_VALU', 0) / n), "valu_per_wave": round(d.get('SQ_INSTS_VALU', 0) / w, 1)}
 json.dump({"source": "SQ_INSTS_VALU / SQ_WAVES (rocprofv3 --pmc) of: " + os.environ.get("MIX_CMD", ""), "kernels": summ},
           open(os.environ["MIX_JSON"], "w"), indent=1)
+for (k, i), d in sorted(each.items(), key=lambda e: e[0][1]):
+    print(f"each {k} dispatch {i} waves {d.get('SQ_WAVES', 0):.0f} valu {d.get('SQ_INSTS_VALU', 0):.0f}")
 P
     cat $O/mix_$tag.txt
     rm -rf /tmp/ps1 /tmp/ps2

@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 import svo_amd as S  # noqa: E402
 from svo_amd.scene import Scene  # noqa: E402
 
-KEYS = ("lk_iterations", "tracked", "inliers", "added", "hypotheses", "ransac_rounds", "max_hypotheses",
+KEYS = ("lk_iterations", "tracked", "inliers", "added", "features", "hypotheses", "ransac_rounds", "max_hypotheses",
         "host_ms_wait_post", "host_ms_hyp", "host_ms_fit", "host_ms_wait_score", "host_ms_wait_kf",
         "host_ms_enqueue", "serial_keyframe", "spec_margin")
 
