@@ -477,6 +477,57 @@ int svo_solve_pnp_sqpnp(const double* obj_xyz, const float* img_xy, int n, const
 int svo_epnp_subsets(svo_ctx* ctx, const float* subsets, int m, const double K[9], int device, double* Rt,
                      int* ok);
 
+/* The batched front end's RANSAC kernels, one launch each (test entry points; the
+ * front end does not call them). S sequences of up to cap points: obj f32
+ * [S][cap][3], img f32 [S][cap][2], counts[S] points each (slots past a count are
+ * not read). Each returns SVO_ERR_ARG before anything is launched or written: a
+ * null ctx (svo_sqpnp_fit with device = 0 needs none) or a null array with S > 0,
+ * S / cap / words_cap < 0, a count outside [0, cap] or with more than words_cap
+ * words of 32 bits. S = 0 is valid.
+ *
+ * svo_pnp_score: the scoring of a RANSAC round (pnp_score_kernel, one block per
+ * hypothesis and sequence): hyps f64 [S][m_stride][12] (R row-major, t), the first
+ * m rows of every sequence scored as svo_pnp_residuals scores them (err <=
+ * thresh2); bits u32 [S][m_stride][words_cap], bit i & 31 of word i / 32 = point i
+ * an inlier, and cnt i32 [S][m_stride], the inliers per row. bits and cnt are read
+ * as well: rows >= m and words >= (count + 31) / 32 come back as given. Also
+ * SVO_ERR_ARG: m < 0, m_stride < 1, m > m_stride. */
+int svo_pnp_score(svo_ctx* ctx, const float* obj, const float* img, const int* counts, int S, int cap,
+                  const double* hyps, int m, int m_stride, const double K[9], float thresh2, uint32_t* bits,
+                  int words_cap, int* cnt);
+
+/* svo_sqpnp_stats: SQPnP's 40 sufficient statistics (svo_sqpnp_fit's input) of the
+ * points of every sequence whose bit is set in bits u32 [S][words_cap]
+ * (suffstats_kernel: one 256-thread block per sequence; thread k sums its points
+ * k, k + 256, ... in order, a 64-lane xor butterfly, then ((w0 + w1) + w2) + w3):
+ * stats f64 [S][40] = n, sum x, sum y, sum (x^2 + y^2), sum c X for c in (1, x, y,
+ * x^2 + y^2), sum c X X^T (6 unique entries each), (x, y) = ((u - cx) / fx, (v -
+ * cy) / fy). Bits at or above a count are ignored. */
+int svo_sqpnp_stats(svo_ctx* ctx, const float* obj, const float* img, const int* counts, int S, int cap,
+                    const uint32_t* bits, int words_cap, const double K[9], double* stats);
+
+/* svo_sqpnp_fit: the final SQPnP fit of every sequence from its statistics and
+ * the pose the front end reports. mode[S]: 0 no model (pose6 = 0, pose12 the
+ * identity), 1 fit on the points of `bits` (R [S][9], t [S][3]: the RANSAC model,
+ * kept where SQPnP asserts or finds nothing in front of the camera), 2 given (rv
+ * [S][3], t: passed through). device = 1: the device fit (launch_sqpnp_fit);
+ * device = 0: what the front end's host pool runs (RansacSeq::fit, then
+ * Frame::pose()). pose6 [S][6] = (rvec, tvec), pose12 [S][12] = camera -> world
+ * (R^T row-major, -R^T t). Also SVO_ERR_ARG: a mode outside 0..2, device outside
+ * 0..1. */
+int svo_sqpnp_fit(svo_ctx* ctx, const double* stats, const int* mode, const double* R, const double* t,
+                  const double* rv, const float* obj, const int* counts, int S, int cap, const uint32_t* bits,
+                  int words_cap, int device, double* pose6, double* pose12);
+
+/* svo_trig_pa (test view): the sin / cos / acos of the final fit's rotation vector and
+ * Frame::pose() (trig_pa.hpp: double-double in plain arithmetic, the same
+ * operations on host and device) on n arguments. fn = 0: out[2 i] = sin x_i, out[2 i
+ * + 1] = cos x_i (0 <= x <= 8; outside, the maths library's); fn = 1: out[2 i] =
+ * acos x_i, out[2 i + 1] = 0. device = 0: on the host (no context needed); 1: on
+ * the GPU. SVO_ERR_ARG: n < 0, fn outside 0..1, device outside 0..1, a null array
+ * with n > 0, device = 1 without a context. */
+int svo_trig_pa(svo_ctx* ctx, const double* x, int n, int fn, int device, double* out);
+
 /* ------------------------------------------------------------ triangulation
  * cv::triangulatePoints(P1, P2, pts1, pts2, points4D) then
  * cv::convertPointsFromHomogeneous (R:src/tracking.cpp:125-131). P1, P2: 3x4

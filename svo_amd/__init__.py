@@ -96,6 +96,7 @@ _i8p = C.POINTER(C.c_int8)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int)
+_u32p = C.POINTER(C.c_uint32)
 _vp = C.c_void_p
 
 # (name, restype, argtypes) for every symbol include/svo_gpu.h declares
@@ -163,6 +164,12 @@ _SIGS = [
                                        C.c_double, _f64p, _f64p, _i32p, _i32p]),
     ("svo_epnp_subsets", C.c_int, [_vp, _f32p, C.c_int, _f64p, C.c_int, _f64p, _i32p]),
     ("svo_solve_pnp_sqpnp", C.c_int, [_f64p, _f32p, C.c_int, _f64p, _f64p, _f64p]),
+    ("svo_pnp_score", C.c_int, [_vp, _f32p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, _f64p, C.c_float,
+                                _u32p, C.c_int, _i32p]),
+    ("svo_sqpnp_stats", C.c_int, [_vp, _f32p, _f32p, _i32p, C.c_int, C.c_int, _u32p, C.c_int, _f64p, _f64p]),
+    ("svo_sqpnp_fit", C.c_int, [_vp, _f64p, _i32p, _f64p, _f64p, _f64p, _f32p, _i32p, C.c_int, C.c_int, _u32p,
+                                C.c_int, C.c_int, _f64p, _f64p]),
+    ("svo_trig_pa", C.c_int, [_vp, _f64p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("svo_triangulate_points", C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p]),
     ("svo_reprojection_jacobians", C.c_int, [_vp, _f64p, _f32p, _i32p, C.c_int, C.c_int, _f64p, _f64p,
                                              C.c_double, _f64p, _f64p, _f64p]),
@@ -297,6 +304,19 @@ def match_filter(idx_qt, dist_qt, idx_tq=None, ratio_pct: int = 80, cap=None) ->
     if rc != 0:
         raise SvoError("svo_match_filter: bad arguments (negative ratio, or an index past the reverse match)")
     return pairs[: min(n.value, cap)].copy()
+
+
+def trig_pa(x, fn: str, ctx=None) -> np.ndarray:
+    """svo_trig_pa (test view): the final fit's plain-arithmetic trigonometry on the arguments
+    x. fn "sincos" -> (n, 2) = (sin, cos); "acos" -> (n,). ctx None: on the host; a Context:
+    on its GPU."""
+    x = _c(x, np.float64).reshape(-1)
+    out = np.full((len(x), 2), np.nan)
+    rc = lib().svo_trig_pa(None if ctx is None else ctx.handle, _p(x, _f64p), len(x), {"sincos": 0, "acos": 1}[fn],
+                           0 if ctx is None else 1, _p(out, _f64p))
+    if rc != 0:
+        raise SvoError(f"svo_trig_pa: error {rc}")
+    return out if fn == "sincos" else out[:, 0].copy()
 
 
 def pose_from_rvec(rvec, tvec) -> np.ndarray:
@@ -1106,6 +1126,70 @@ class Context:
         self._check(lib().svo_epnp_subsets(self.handle, _p(subsets, _f32p), m, _p(K, _f64p), int(device),
                                            _p(Rt, _f64p), _p(ok, _i32p)))
         return Rt, ok
+
+    def pnp_score(self, obj, img_pts, counts, hyps, m, K, thresh2, bits, cnt):
+        """svo_pnp_score (test view): the front end's scoring kernel on S sequences. obj (S, cap, 3)
+        f32, img_pts (S, cap, 2) f32, counts (S,), hyps (S, m_stride, 12) f64 of which the first m
+        rows are scored; bits (S, m_stride, words_cap) u32 and cnt (S, m_stride) i32 are read and
+        written in place (what the kernel leaves alone keeps the caller's values) and returned."""
+        obj = _c(obj, np.float32)
+        img_pts = _c(img_pts, np.float32)
+        counts = _c(counts, np.int32)
+        hyps = _c(hyps, np.float64)
+        K = _c(K, np.float64).reshape(9)
+        S, cap = obj.shape[0], obj.shape[1]
+        m_stride, words_cap = bits.shape[1], bits.shape[2]
+        if (obj.shape != (S, cap, 3) or img_pts.shape != (S, cap, 2) or counts.shape != (S,)
+                or hyps.shape != (S, m_stride, 12) or cnt.shape != (S, m_stride)
+                or bits.dtype != np.uint32 or cnt.dtype != np.int32
+                or not bits.flags.c_contiguous or not cnt.flags.c_contiguous):
+            raise ValueError("pnp_score: shapes / dtypes")
+        self._check(lib().svo_pnp_score(self.handle, _p(obj, _f32p), _p(img_pts, _f32p), _p(counts, _i32p), S, cap,
+                                        _p(hyps, _f64p), int(m), m_stride, _p(K, _f64p), float(thresh2),
+                                        _p(bits, _u32p), words_cap, _p(cnt, _i32p)))
+        return bits, cnt
+
+    def sqpnp_stats(self, obj, img_pts, counts, bits, K):
+        """svo_sqpnp_stats (test view): SQPnP's 40 sufficient statistics of the points whose bit is
+        set, per sequence (the front end's suffstats kernel). obj (S, cap, 3) f32, img_pts (S, cap, 2)
+        f32, counts (S,), bits (S, words_cap) u32 -> (S, 40) f64."""
+        obj = _c(obj, np.float32)
+        img_pts = _c(img_pts, np.float32)
+        counts = _c(counts, np.int32)
+        bits = _c(bits, np.uint32)
+        K = _c(K, np.float64).reshape(9)
+        S, cap = obj.shape[0], obj.shape[1]
+        if obj.shape != (S, cap, 3) or img_pts.shape != (S, cap, 2) or counts.shape != (S,) or bits.shape[:1] != (S,) \
+                or bits.ndim != 2:
+            raise ValueError("sqpnp_stats: shapes")
+        stats = np.full((S, 40), np.nan)
+        self._check(lib().svo_sqpnp_stats(self.handle, _p(obj, _f32p), _p(img_pts, _f32p), _p(counts, _i32p), S, cap,
+                                          _p(bits, _u32p), bits.shape[1], _p(K, _f64p), _p(stats, _f64p)))
+        return stats
+
+    def sqpnp_fit(self, stats, mode, R, t, rv, obj, counts, bits, device=True):
+        """svo_sqpnp_fit (test view): the final SQPnP fits from the statistics of sqpnp_stats and
+        the poses the front end reports -> (pose6 (S, 6) = (rvec, tvec), pose12 (S, 12) camera ->
+        world). mode (S,): 0 no model, 1 fit (R (S, 9), t (S, 3): the RANSAC model to fall back
+        to), 2 given (rv (S, 3), t). device True: the device fit; False: the host pool's code."""
+        stats = _c(stats, np.float64).reshape(-1, 40)
+        S = len(stats)
+        mode = _c(mode, np.int32).reshape(S)
+        R = _c(R, np.float64).reshape(S, 9)
+        t = _c(t, np.float64).reshape(S, 3)
+        rv = _c(rv, np.float64).reshape(S, 3)
+        obj = _c(obj, np.float32)
+        counts = _c(counts, np.int32).reshape(S)
+        bits = _c(bits, np.uint32)
+        if obj.ndim != 3 or obj.shape[0] != S or obj.shape[2] != 3 or bits.ndim != 2 or bits.shape[0] != S:
+            raise ValueError("sqpnp_fit: shapes")
+        pose6 = np.full((S, 6), np.nan)
+        pose12 = np.full((S, 12), np.nan)
+        self._check(lib().svo_sqpnp_fit(self.handle, _p(stats, _f64p), _p(mode, _i32p), _p(R, _f64p), _p(t, _f64p),
+                                        _p(rv, _f64p), _p(obj, _f32p), _p(counts, _i32p), S, obj.shape[1],
+                                        _p(bits, _u32p), bits.shape[1], int(bool(device)), _p(pose6, _f64p),
+                                        _p(pose12, _f64p)))
+        return pose6, pose12
 
     def triangulate_points(self, P1, P2, pts1, pts2):
         """cv::triangulatePoints + convertPointsFromHomogeneous -> (xyzw (n,4), xyz (n,3)) float32."""

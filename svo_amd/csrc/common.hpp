@@ -82,6 +82,7 @@ enum ScratchSlot {
     kScratchRectify,    // svo_image_upload_raw, svo_remap: the raw frame (the one slot whose users
                         // synchronise as they enter: upload_raw returns with its kernel in flight)
     kScratchRefine,     // refine_device.cpp's entries, svo_frontend_refine_poses
+    kScratchFit,        // svo_pnp_score, svo_sqpnp_stats, svo_sqpnp_fit, svo_trig_pa
     kScratchSlots       // the count
 };
 }  // namespace svo
@@ -421,6 +422,8 @@ size_t sqpnp_fit_work_bytes(int nseq);
 hipError_t launch_sqpnp_fit(const double* stats, const SqpnpFitIn* in, const float* obj, const int* counts, int cap,
                             const uint32_t* bits, int words_cap, int nseq, double* pose6, double* pose12, void* work,
                             hipStream_t st);
+// trig_pa.hpp's functions on n arguments: fn 0 -> out[2 i] = sin, out[2 i + 1] = cos; fn 1 -> out[2 i] = acos
+hipError_t launch_trig_pa(const double* x, int n, int fn, double* out, hipStream_t st);
 size_t bucket_scratch_ints(int img_w, int img_h, int bucket, int per_bucket, int n);
 hipError_t launch_bucket(const BucketBatch& b, int nseq, int img_w, int img_h, int bucket, int per_bucket,
                          hipStream_t st);

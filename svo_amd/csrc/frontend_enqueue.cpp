@@ -300,17 +300,7 @@ PendingMap fe_pending(svo_frontend* fe) {
 // the solvePnPRansac model [R(rvec) | tvec] (svo::SE3d::inverse), identity
 // when RANSAC found no model (rvec = tvec = 0, as the host mirror)
 void fe_set_pose(svo_frontend* fe, int s, bool ok, const double rvec[3], const double tvec[3]) {
-    double* T = fe->h_pose + 12 * (size_t)s;
-    double R[9];
-    const double zero[3] = {0, 0, 0};
-    if (!ok) {
-        rvec = zero;
-        tvec = zero;
-    }
-    la::rodrigues(rvec, R);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) T[3 * i + j] = R[3 * j + i];
-    for (int i = 0; i < 3; i++) T[9 + i] = -(T[3 * i] * tvec[0] + T[3 * i + 1] * tvec[1] + T[3 * i + 2] * tvec[2]);
+    pose_cam_to_world(ok, rvec, tvec, fe->h_pose + 12 * (size_t)s);
 }
 
 // svo_frontend_set_stereo_tracking: the right columns of frame t's tracked features
@@ -402,7 +392,7 @@ static void fe_window_pose(svo_frontend* fe) {
     for (int s = 0; s < fe->S; s++) {
         const double* P = &fe->pose[6 * (size_t)s];
         double* T = w.h_pose + 12 * ((size_t)s * w.slots + slot);
-        la::rodrigues(P, T);
+        la::rodrigues<true>(P, T);  // (the functions h_pose is built with: pose_cam_to_world)
         std::memcpy(T + 9, P + 3, sizeof(double) * 3);
     }
 }
@@ -458,16 +448,8 @@ double fe_finish_fits(svo_frontend* fe) {
     } else {
         (void)hipEventSynchronize(fe->ev_full_b[fe->ahead.fit_parity]);  // cheirality test reads h_obj
         fe->pool->run(fe->S, [&](int s) {
-            RansacSeq& r = fe->rs[s];
-            r.fit(fe->cfg.K, fe->h_stats + kSqpnpStats * (size_t)s);
-            double* P = &fe->pose[6 * (size_t)s];
-            if (r.ok) {
-                std::memcpy(P, r.rvec, sizeof(r.rvec));
-                std::memcpy(P + 3, r.tvec, sizeof(r.tvec));
-            } else {
-                std::fill(P, P + 6, 0.0);
-            }
-            fe_set_pose(fe, s, r.ok, P, P + 3);
+            fit_pose(fe->rs[s], fe->cfg.K, fe->h_stats + kSqpnpStats * (size_t)s, &fe->pose[6 * (size_t)s],
+                     fe->h_pose + 12 * (size_t)s);
         });
     }
     fe_window_pose(fe);

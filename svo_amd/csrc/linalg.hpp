@@ -7,6 +7,8 @@
 
 #include <cmath>
 
+#include "trig_pa.hpp"
+
 namespace svo {
 namespace la {
 
@@ -568,7 +570,10 @@ SVO_HD void nearest_rotation(const double* M, double* R) {
     }
 }
 
-// Rodrigues vector -> matrix (cv::Rodrigues formula order).
+// Rodrigues vector -> matrix (cv::Rodrigues formula order). PA: sin and cos in
+// plain arithmetic (trig_pa.hpp) instead of the maths library's, where the host
+// and the device must give the same bits (the final fit's Frame::pose()).
+template <bool PA = false>
 SVO_HD void rodrigues(const double* rv, double* R) {
     double rx = rv[0], ry = rv[1], rz = rv[2];
     const double th = sqrt(rx * rx + ry * ry + rz * rz);
@@ -576,7 +581,14 @@ SVO_HD void rodrigues(const double* rv, double* R) {
         for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
         return;
     }
-    const double c = cos(th), s = sin(th), c1 = 1. - c, it = th ? 1. / th : 0.;
+    double c, s;
+    if (PA) {
+        pa::sincos(th, &s, &c);
+    } else {
+        c = cos(th);
+        s = sin(th);
+    }
+    const double c1 = 1. - c, it = th ? 1. / th : 0.;
     rx *= it;
     ry *= it;
     rz *= it;
@@ -986,7 +998,9 @@ SVO_HD void invert_svd(const double* A, double* Ai) {
 }
 
 // cv::Rodrigues matrix -> vector: SVD::compute(R, W, U, Vt), R = U * Vt (Matx
-// product), then the axis-angle extraction (same as la::rodrigues_inv's)
+// product), then the axis-angle extraction (same as la::rodrigues_inv's). PA: acos
+// in plain arithmetic (trig_pa.hpp): the final fit's rvec, host and device alike.
+template <bool PA = false>
 SVO_HD void rodrigues_inv(const double* Rin, double* rv) {
     double w[3], u[9], vt[9], R[9];
     svd<3>(Rin, w, u, vt);
@@ -1000,7 +1014,7 @@ SVO_HD void rodrigues_inv(const double* Rin, double* rv) {
     const double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
     double c = (R[0] + R[4] + R[8] - 1) * 0.5;
     c = c > 1. ? 1. : c < -1. ? -1. : c;
-    double th = acos(c);
+    double th = PA ? pa::acos(c) : acos(c);
     if (s < 1e-5) {
         if (c > 0) {
             rx = ry = rz = 0;

@@ -434,10 +434,10 @@ __global__ __launch_bounds__(64) void sqpnp_select_kernel(const SqpnpFitIn* __re
                 R, t, &found);
         }
         if (found) {
-            la::cv::rodrigues_inv(R, rvec);
+            la::cv::rodrigues_inv<true>(R, rvec);
             for (int k = 0; k < 3; k++) tvec[k] = t[k];
         } else {  // solvePnP(SQPNP) asserted or found nothing: the RANSAC model (as the host)
-            la::cv::rodrigues_inv(fin.R, rvec);
+            la::cv::rodrigues_inv<true>(fin.R, rvec);
             for (int k = 0; k < 3; k++) tvec[k] = fin.t[k];
         }
     }
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(64) void sqpnp_select_kernel(const SqpnpFitIn* __re
     }
     // Frame::pose(): the inverse of [R(rvec) | tvec] (svo::SE3d::inverse order)
     double Rm[9];
-    la::rodrigues(rvec, Rm);
+    la::rodrigues<true>(rvec, Rm);
     double* T = pose12 + 12 * (size_t)s;
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) T[3 * i + j] = Rm[3 * j + i];
@@ -467,6 +467,28 @@ hipError_t launch_sqpnp_fit(const double* stats, const SqpnpFitIn* in, const flo
     hipLaunchKernelGGL(sqpnp_sqp_kernel, dim3(9, nseq), dim3(64), 0, st, in, wk);
     hipLaunchKernelGGL(sqpnp_select_kernel, dim3(nseq), dim3(64), 0, st, in, wk, obj, counts, cap, bits, words_cap,
                        pose6, pose12);
+    return hipGetLastError();
+}
+
+namespace {
+
+// trig_pa.hpp on the device, one argument per thread (svo_trig_pa: its test view)
+__global__ void trig_pa_kernel(const double* __restrict__ x, int n, int fn, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (fn == 0) {
+        la::pa::sincos(x[i], &out[2 * i], &out[2 * i + 1]);
+    } else {
+        out[2 * i] = la::pa::acos(x[i]);
+        out[2 * i + 1] = 0;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_trig_pa(const double* x, int n, int fn, double* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(trig_pa_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n, fn, out);
     return hipGetLastError();
 }
 

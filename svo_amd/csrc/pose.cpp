@@ -17,6 +17,7 @@
 //   t = P r), from statistics summed on the GPU -- and its solution search over
 //   Omega's eigenvectors with the same SQP runs (15 steps at most: an unconverged
 //   run can win, as in OpenCV).
+#include <algorithm>
 #include <cfloat>
 #include <cstring>
 #include <vector>
@@ -271,7 +272,7 @@ void RansacSeq::select(const double K[9], bool list) {
     if (direct) {
         double R[9], t[3];
         if (!epnp_pixels(obj, img, nullptr, n, K, R, t)) return;
-        la::cv::rodrigues_inv(R, rvec);
+        la::cv::rodrigues_inv<true>(R, rvec);
         std::memcpy(tvec, t, sizeof(t));
         for (int i = 0; i < n; i++) inliers.push_back(i);
         for (int i = 0; i < n; i++) best[i >> 5] |= 1u << (i & 31);
@@ -318,7 +319,7 @@ void RansacSeq::fit(const double K[9], const double* sums) {
     sqpnp_assemble(sums, c);
     fitted = true;
     if (!c.ok) {  // solvePnP(SQPNP) would assert: keep the RANSAC model (as the oracle)
-        la::cv::rodrigues_inv(bestR, rvec);
+        la::cv::rodrigues_inv<true>(bestR, rvec);
         std::memcpy(tvec, bestt, sizeof(bestt));
         return;
     }
@@ -334,17 +335,41 @@ void RansacSeq::fit(const double K[9], const double* sums) {
         },
         Rf, tf, &found);
     if (!found) {  // no solution in front of the camera: solvePnP fails, keep the RANSAC model
-        la::cv::rodrigues_inv(bestR, rvec);
+        la::cv::rodrigues_inv<true>(bestR, rvec);
         std::memcpy(tvec, bestt, sizeof(bestt));
         return;
     }
-    la::cv::rodrigues_inv(Rf, rvec);
+    la::cv::rodrigues_inv<true>(Rf, rvec);
     std::memcpy(tvec, tf, sizeof(tf));
 }
 
 void RansacSeq::finish(const double K[9]) {
     select(K);
     fit(K, nullptr);
+}
+
+void pose_cam_to_world(bool ok, const double rvec[3], const double tvec[3], double T[12]) {
+    double R[9];
+    const double zero[3] = {0, 0, 0};
+    if (!ok) {
+        rvec = zero;
+        tvec = zero;
+    }
+    la::rodrigues<true>(rvec, R);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) T[3 * i + j] = R[3 * j + i];
+    for (int i = 0; i < 3; i++) T[9 + i] = -(T[3 * i] * tvec[0] + T[3 * i + 1] * tvec[1] + T[3 * i + 2] * tvec[2]);
+}
+
+void fit_pose(RansacSeq& r, const double K[9], const double* sums, double P6[6], double T[12]) {
+    r.fit(K, sums);
+    if (r.ok) {
+        std::memcpy(P6, r.rvec, sizeof(r.rvec));
+        std::memcpy(P6 + 3, r.tvec, sizeof(r.tvec));
+    } else {
+        std::fill(P6, P6 + 6, 0.0);
+    }
+    pose_cam_to_world(r.ok, P6, P6 + 3, T);
 }
 
 }  // namespace svo
@@ -371,7 +396,7 @@ extern "C" int svo_solve_pnp_sqpnp(const double* obj_xyz, const float* img_xy, i
     fit_from_cost(
         c, n, [&](int k, double* p) { std::memcpy(p, obj_xyz + 3 * (size_t)k, sizeof(double) * 3); }, R, t, &found);
     if (!found) return 0;
-    la::cv::rodrigues_inv(R, rvec);
+    la::cv::rodrigues_inv<true>(R, rvec);
     std::memcpy(tvec, t, sizeof(t));
     return 1;
 }
@@ -436,4 +461,184 @@ extern "C" int svo_solve_pnp_ransac(svo_ctx* ctx, const double* obj_xyz, const f
         for (size_t i = 0; i < rs.inliers.size(); i++) inliers[i] = rs.inliers[i];
     if (n_inliers) *n_inliers = (int)rs.inliers.size();
     return 1;
+}
+
+// ---- the batched front end's RANSAC kernels, one at a time (test entry points) ----
+namespace {
+
+// the batch's shape as the kernels index it: every count within [0, cap] and
+// within the bit words of a row
+bool batch_counts_ok(const int* counts, int S, int cap, int words_cap) {
+    for (int s = 0; s < S; s++)
+        if (counts[s] < 0 || counts[s] > cap || (counts[s] + 31) / 32 > words_cap) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int svo_pnp_score(svo_ctx* ctx, const float* obj, const float* img, const int* counts, int S, int cap,
+                             const double* hyps, int m, int m_stride, const double K[9], float thresh2,
+                             uint32_t* bits, int words_cap, int* cnt) {
+    using namespace svo;
+    if (!ctx || !K || S < 0 || cap < 0 || m < 0 || m_stride < 1 || m > m_stride || words_cap < 0 ||
+        (S > 0 && (!obj || !img || !counts || !hyps || !bits || !cnt)) ||
+        (S > 0 && !batch_counts_ok(counts, S, cap, words_cap)))
+        return set_error(ctx, SVO_ERR_ARG, "svo_pnp_score: bad arguments");
+    if (S == 0 || m == 0) return SVO_OK;
+    const size_t rows = (size_t)S * m_stride;
+    float *dobj, *dimg;
+    int *dn, *dcnt;
+    double* dh;
+    uint32_t* dbits;
+    if (!carve_scratch(ctx, kScratchFit, [&](Carver& c) {
+            dobj = c.take<float>(3 * (size_t)S * cap);
+            dimg = c.take<float>(2 * (size_t)S * cap);
+            dn = c.take<int>(S);
+            dh = c.take<double>(12 * rows);
+            dbits = c.take<uint32_t>(rows * words_cap);
+            dcnt = c.take<int>(rows);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(dobj, obj, sizeof(float) * 3 * (size_t)S * cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dimg, img, sizeof(float) * 2 * (size_t)S * cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dn, counts, sizeof(int) * (size_t)S, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dh, hyps, sizeof(double) * 12 * rows, hipMemcpyHostToDevice, st));
+    // the caller's bits and counts go in, so what the kernel leaves alone comes back as given
+    SVO_HIP(ctx, hipMemcpyAsync(dbits, bits, sizeof(uint32_t) * rows * words_cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dcnt, cnt, sizeof(int) * rows, hipMemcpyHostToDevice, st));
+    PnpBatch pb{dobj, dimg, dn, 0, cap, dh, m, nullptr, dbits, words_cap, dcnt};
+    pb.mstride = m_stride;  // (as ransac_score_and_consume: rows at a fixed stride, m of them scored)
+    SVO_HIP(ctx, launch_pnp_score(pb, S, K[0], K[4], K[2], K[5], thresh2, st));
+    SVO_HIP(ctx, hipMemcpyAsync(bits, dbits, sizeof(uint32_t) * rows * words_cap, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(cnt, dcnt, sizeof(int) * rows, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+extern "C" int svo_sqpnp_stats(svo_ctx* ctx, const float* obj, const float* img, const int* counts, int S, int cap,
+                               const uint32_t* bits, int words_cap, const double K[9], double* stats) {
+    using namespace svo;
+    if (!ctx || !K || S < 0 || cap < 0 || words_cap < 0 || (S > 0 && (!obj || !img || !counts || !bits || !stats)) ||
+        (S > 0 && !batch_counts_ok(counts, S, cap, words_cap)))
+        return set_error(ctx, SVO_ERR_ARG, "svo_sqpnp_stats: bad arguments");
+    if (S == 0) return SVO_OK;
+    float *dobj, *dimg;
+    int* dn;
+    uint32_t* dbits;
+    double* dstats;
+    if (!carve_scratch(ctx, kScratchFit, [&](Carver& c) {
+            dobj = c.take<float>(3 * (size_t)S * cap);
+            dimg = c.take<float>(2 * (size_t)S * cap);
+            dn = c.take<int>(S);
+            dbits = c.take<uint32_t>((size_t)S * words_cap);
+            dstats = c.take<double>(kSqpnpStats * (size_t)S);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(dobj, obj, sizeof(float) * 3 * (size_t)S * cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dimg, img, sizeof(float) * 2 * (size_t)S * cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dn, counts, sizeof(int) * (size_t)S, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dbits, bits, sizeof(uint32_t) * (size_t)S * words_cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, launch_suffstats(dobj, dimg, dn, cap, dbits, words_cap, S, K, dstats, st));
+    SVO_HIP(ctx, hipMemcpyAsync(stats, dstats, sizeof(double) * kSqpnpStats * (size_t)S, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+extern "C" int svo_sqpnp_fit(svo_ctx* ctx, const double* stats, const int* mode, const double* R, const double* t,
+                             const double* rv, const float* obj, const int* counts, int S, int cap,
+                             const uint32_t* bits, int words_cap, int device, double* pose6, double* pose12) {
+    using namespace svo;
+    bool ok = (device == 0 || (device == 1 && ctx)) && S >= 0 && cap >= 0 && words_cap >= 0 &&
+              (S == 0 || (stats && mode && R && t && rv && obj && counts && bits && pose6 && pose12));
+    if (ok && S > 0) ok = batch_counts_ok(counts, S, cap, words_cap);
+    for (int s = 0; ok && s < S; s++) ok = mode[s] >= 0 && mode[s] <= 2;
+    if (!ok) return set_error(ctx, SVO_ERR_ARG, "svo_sqpnp_fit: bad arguments");
+    if (S == 0) return SVO_OK;
+    if (device == 0) {  // what the front end's host pool runs from the same statistics (fe_finish_fits)
+        // (the fit reads K only to sum statistics it is not given)
+        const double noK[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        for (int s = 0; s < S; s++) {
+            RansacSeq r;  // the sequence as step_select leaves it
+            r.obj = obj + 3 * (size_t)s * cap;
+            r.n = counts[s];
+            r.best.assign(bits + (size_t)s * words_cap, bits + (size_t)s * words_cap + (r.n + 31) / 32);
+            std::memcpy(r.bestR, R + 9 * (size_t)s, sizeof(r.bestR));
+            std::memcpy(r.bestt, t + 3 * (size_t)s, sizeof(r.bestt));
+            r.ok = mode[s] != 0;
+            r.fitted = mode[s] == 2;
+            if (r.fitted) {
+                std::memcpy(r.rvec, rv + 3 * (size_t)s, sizeof(r.rvec));
+                std::memcpy(r.tvec, t + 3 * (size_t)s, sizeof(r.tvec));
+            }
+            fit_pose(r, noK, stats + kSqpnpStats * (size_t)s, pose6 + 6 * (size_t)s, pose12 + 12 * (size_t)s);
+        }
+        return SVO_OK;
+    }
+    std::vector<SqpnpFitIn> in((size_t)S);
+    for (int s = 0; s < S; s++) {
+        in[s].mode = mode[s];
+        in[s].pad = 0;
+        std::memcpy(in[s].R, R + 9 * (size_t)s, sizeof(in[s].R));
+        std::memcpy(in[s].t, t + 3 * (size_t)s, sizeof(in[s].t));
+        std::memcpy(in[s].rv, rv + 3 * (size_t)s, sizeof(in[s].rv));
+    }
+    double *dstats, *dp6, *dp12;
+    SqpnpFitIn* din;
+    float* dobj;
+    int* dn;
+    uint32_t* dbits;
+    char* dwork;
+    if (!carve_scratch(ctx, kScratchFit, [&](Carver& c) {
+            dstats = c.take<double>(kSqpnpStats * (size_t)S);
+            din = c.take<SqpnpFitIn>((size_t)S);
+            dobj = c.take<float>(3 * (size_t)S * cap);
+            dn = c.take<int>(S);
+            dbits = c.take<uint32_t>((size_t)S * words_cap);
+            dp6 = c.take<double>(6 * (size_t)S);
+            dp12 = c.take<double>(12 * (size_t)S);
+            dwork = c.take<char>(sqpnp_fit_work_bytes(S));
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    hipStream_t st = ctx->stream;
+    SVO_HIP(ctx, hipMemcpyAsync(dstats, stats, sizeof(double) * kSqpnpStats * (size_t)S, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(din, in.data(), sizeof(SqpnpFitIn) * (size_t)S, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dobj, obj, sizeof(float) * 3 * (size_t)S * cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dn, counts, sizeof(int) * (size_t)S, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, hipMemcpyAsync(dbits, bits, sizeof(uint32_t) * (size_t)S * words_cap, hipMemcpyHostToDevice, st));
+    SVO_HIP(ctx, launch_sqpnp_fit(dstats, din, dobj, dn, cap, dbits, words_cap, S, dp6, dp12, dwork, st));
+    SVO_HIP(ctx, hipMemcpyAsync(pose6, dp6, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipMemcpyAsync(pose12, dp12, sizeof(double) * 12 * (size_t)S, hipMemcpyDeviceToHost, st));
+    SVO_HIP(ctx, hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
+extern "C" int svo_trig_pa(svo_ctx* ctx, const double* x, int n, int fn, int device, double* out) {
+    using namespace svo;
+    if ((device != 0 && !(device == 1 && ctx)) || n < 0 || fn < 0 || fn > 1 || (n > 0 && (!x || !out)))
+        return set_error(ctx, SVO_ERR_ARG, "svo_trig_pa: bad arguments");
+    if (n == 0) return SVO_OK;
+    if (device == 0) {
+        for (int i = 0; i < n; i++) {
+            if (fn == 0) {
+                la::pa::sincos(x[i], &out[2 * i], &out[2 * i + 1]);
+            } else {
+                out[2 * i] = la::pa::acos(x[i]);
+                out[2 * i + 1] = 0;
+            }
+        }
+        return SVO_OK;
+    }
+    double *dx, *dout;
+    if (!carve_scratch(ctx, kScratchFit, [&](Carver& c) {
+            dx = c.take<double>((size_t)n);
+            dout = c.take<double>(2 * (size_t)n);
+        }))
+        return set_error(ctx, SVO_ERR_HIP, "scratch alloc");
+    SVO_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    SVO_HIP(ctx, launch_trig_pa(dx, n, fn, dout, ctx->stream));
+    SVO_HIP(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
 }

@@ -101,4 +101,12 @@ struct RansacSeq {
 constexpr int kSqpnpStats = 40;
 void sqpnp_sums(const double* pw, const double* q, int n, double* sums);
 
+// Frame::pose(): camera -> world of [R(rvec) | tvec], T = (R^T row-major, -R^T t)
+// (svo::SE3d::inverse order); the identity when !ok
+void pose_cam_to_world(bool ok, const double rvec[3], const double tvec[3], double T[12]);
+// One sequence's final fit from its statistics as the front end's host pool runs
+// it (fe_finish_fits; svo_sqpnp_fit's host leg): r.fit, then P6 = (rvec, tvec), or
+// zeros without a model, and T = pose_cam_to_world of it
+void fit_pose(RansacSeq& r, const double K[9], const double* sums, double P6[6], double T[12]);
+
 }  // namespace svo
