@@ -615,6 +615,101 @@ int svo_refine_poses_time(svo_ctx* ctx, const double* obj_xyz, const float* img_
                           double huber_delta, int max_iterations, const double* poses, int reps, double* ms_device,
                           double* ms_host);
 
+/* ------------------------------------------------------------ pose-graph optimisation (§10)
+ * The back end behind place recognition: the poses of many frames from relative-
+ * pose measurements between them, odometry edges and loop edges alike, by a robust
+ * least squares over all poses at once. P problems of up to max_nodes <=
+ * SVO_PG_MAX_NODES nodes and max_edges <= SVO_PG_MAX_EDGES edges each; n_nodes /
+ * n_edges: P counts, or NULL = the maximum (a ragged batch, as svo_bundle_adjust's).
+ * Node i is a pose T_i = [R|t], world -> camera, 12 doubles, R row-major (poses:
+ * P*max_nodes*12). fixed (P*max_nodes bytes): non-zero holds the node; a problem
+ * with no fixed node is allowed -- the damping makes the system solvable, and the
+ * result keeps whatever gauge the start had. An edge (edge_ij: P*max_edges pairs
+ * i, j; edge_Z: 12 doubles; edge_info: 21 doubles) measures Z ~ T_j T_i^-1 with the
+ * symmetric 6x6 information matrix Omega, given as its upper triangle row-major in
+ * the order (rho, phi): the first 21 entries of svo_refine_poses_stereo's normal,
+ * so a refined pose's information is handed in as it is.
+ *   A = T_j T_i^-1, E = A Z^-1 = [R_e | t_e], e = (t_e, log R_e);
+ *   log R = f(th) v, v = 1/2 vee(R - R'), th = acos(clamp((tr R - 1)/2, -1, 1)),
+ *   f = th / sin th, and 1 + th^2/6 for th < 1e-4; acos, sin and cos in plain
+ *   arithmetic (svo_trig_pa's), so an edge's terms are the same bits on host and
+ *   device. The rule is for th < pi: at th = pi, f is 2.6e16 (the sine of the
+ *   double nearest pi), every term stays finite and the edge is not refused.
+ *   Jacobians for T <- exp(xi^) T, xi = (rho, phi):
+ *   D = [[I, -[t_e]x], [0, Jl^-1(log R_e)]], Jl^-1(p) = I - 1/2 [p]x + k [p]x^2,
+ *   k = 1/th^2 - (1 + cos th)/(2 th sin th), and 1/12 for th < 1e-4;
+ *   J_j = D, J_i = -D Ad(A), Ad(A) = [[R_A, [t_A]x R_A], [0, R_A]].
+ *   Cost: q = e' Omega e, s = sqrt(q), Huber on s with huber_delta (<= 0: none):
+ *   w = 1 or delta/s, cost q/2 or delta (s - delta/2). q < 0 (an indefinite Omega)
+ *   adds nothing: w = 0, cost 0.
+ * Levenberg-Marquardt per problem, svo_refine_poses' control: lambda from 1e-4;
+ * H_kk += lambda (H_kk > 0 ? H_kk : 1e-12) on every diagonal entry; the step rule
+ * |dx| < 1e-12 (1 + |t|) over the whole state (dx of every node, t of every node);
+ * T <- exp(xi^) T per free node; accept on c1 <= c0, lambda <- max(0.1 lambda,
+ * 1e-12), stop once c0 - c1 <= 1e-15 c0; else lambda x10, stop at 1e16. The
+ * damped system over the free nodes is solved by conjugate gradients with the
+ * block-Jacobi preconditioner (the Cholesky factor of each node's damped 6x6 block,
+ * svo_refine_poses' arithmetic), from x = 0, until r'z <= (1e-8)^2 r0'z0 or max_cg
+ * products; at that cap the step is used as it stands and the verdict decides. A
+ * diagonal block that is not positive definite, or a p'Ap that is not positive or
+ * not finite, counts as "not positive definite": lambda x10 and solve again, up to
+ * 1e16, where the problem ends. All of it runs in one workgroup of one launch, in
+ * double, with one summation order:
+ *   - a node's diagonal block (21) and gradient (6) are the sums over its incident
+ *     edges in ascending edge index, whichever end it is, starting from the first
+ *     edge's term;
+ *   - row k of the matrix-vector product is the node's damped diagonal block's
+ *     product first, then its incident edges' blocks in that order;
+ *   - every dot product and the cost: thread t of 256 adds entries t, t + 256, ...
+ *     in ascending order; the 64 lanes of a wave by the xor butterfly 32, ..., 1;
+ *     the four waves as ((w0 + w1) + w2) + w3.
+ * Nothing outside the problem enters an order (not n_problems, max_nodes,
+ * max_edges or the other problems): a problem gets the same bits alone and in any
+ * batch, run after run. poses_out (P*max_nodes*12) may be poses. costs: P x 2
+ * (initial, final); iterations: P, the LM iterations each problem began;
+ * cg_iterations: P, the matrix-vector products of the whole run; each may be NULL.
+ * max_iterations == 0: the poses keep their bits and both costs are equal. A
+ * problem with a value that is not finite in a node pose, or within its count in
+ * edge_Z or edge_info, or whose first cost is not finite, is not iterated on: its
+ * poses keep their bits, its costs are NaN, its iteration counts 0, and the other
+ * problems get what they get alone; whatever lies beyond the counts is not read.
+ * SVO_ERR_ARG (nothing launched, nothing written): sizes or counts out of range, a
+ * required pointer NULL, max_iterations outside 0 .. SVO_PG_MAX_ITERATIONS, max_cg
+ * outside 1 .. SVO_PG_MAX_CG (the bounds that keep a launch finite), an edge
+ * within its count with an index outside 0 .. n_nodes - 1 or with i == j.
+ * The launch uses 137 KB of LDS per workgroup (the conjugate gradients' vectors
+ * and the incidence lists) and, per problem at the caps, 1.8 MB of scratch beside
+ * its inputs (720 bytes per edge and 576 per node). */
+#define SVO_PG_MAX_NODES 512
+#define SVO_PG_MAX_EDGES 2048
+#define SVO_PG_MAX_ITERATIONS 200
+#define SVO_PG_MAX_CG 4096
+int svo_pose_graph_optimize(svo_ctx* ctx, int n_problems, int max_nodes, int max_edges, const int* n_nodes,
+                            const int* n_edges, const double* poses, const uint8_t* fixed, const int* edge_ij,
+                            const double* edge_Z, const double* edge_info, double huber_delta, int max_iterations,
+                            int max_cg, double* poses_out, double* costs, int* iterations, int* cg_iterations);
+/* The test view: the first linearisation at the given poses, nothing moved. cost
+ * (P); per edge e (P*max_edges*6), w (P*max_edges), J_i and J_j (P*max_edges*36,
+ * row-major); per node its 21 + 6 sums (P*max_nodes*27). Any output may be NULL;
+ * entries beyond a problem's counts are left as they were. A problem with a value
+ * that is not finite still returns what the arithmetic gives. */
+int svo_pose_graph_linearize(svo_ctx* ctx, int n_problems, int max_nodes, int max_edges, const int* n_nodes,
+                             const int* n_edges, const double* poses, const uint8_t* fixed, const int* edge_ij,
+                             const double* edge_Z, const double* edge_info, double huber_delta, double* cost,
+                             double* edge_e, double* edge_w, double* edge_Ji, double* edge_Jj, double* node_sums);
+/* svo_pose_graph_optimize's launch timed with HIP events: reps launches after one
+ * warm-up, each from `poses` (which stay as they are) -> ms per whole launch.
+ * iterations / cg_iterations (P each, may be NULL): the last launch's counts.
+ * SVO_ERR_ARG in addition: nothing to run, reps <= 0, ms NULL. */
+int svo_pose_graph_time(svo_ctx* ctx, int n_problems, int max_nodes, int max_edges, const int* n_nodes,
+                        const int* n_edges, const double* poses, const uint8_t* fixed, const int* edge_ij,
+                        const double* edge_Z, const double* edge_info, double huber_delta, int max_iterations,
+                        int max_cg, int reps, double* ms, int* iterations, int* cg_iterations);
+/* Z = T_j T_i^-1 (12 doubles each), the measurement an edge (i, j) holds when the
+ * two poses agree with it: built with the solver's own arithmetic, so such an
+ * edge's error is zero to rounding. Host only; -1 on a NULL argument. */
+int svo_pose_graph_edge(const double* Ti, const double* Tj, double* Z);
+
 /* ------------------------------------------------------------ windowed bundle adjustment
  * Poses and points together: the back end the reference promises (Map::run's
  * "TODO optimization part here", R:src/map.cpp) and never builds. P problems,

@@ -179,6 +179,13 @@ _SIGS = [
                                           C.c_double, C.c_int, _f64p, _f64p, _i32p, _f64p]),
     ("svo_refine_poses_time", C.c_int, [_vp, _f64p, _f32p, _f32p, _i32p, C.c_int, C.c_int, _f64p, C.c_double,
                                         C.c_double, C.c_int, _f64p, C.c_int, _f64p, _f64p]),
+    ("svo_pose_graph_optimize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f64p, _u8p, _i32p, _f64p,
+                                          _f64p, C.c_double, C.c_int, C.c_int, _f64p, _f64p, _i32p, _i32p]),
+    ("svo_pose_graph_linearize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f64p, _u8p, _i32p, _f64p,
+                                           _f64p, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    ("svo_pose_graph_time", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f64p, _u8p, _i32p, _f64p, _f64p,
+                                      C.c_double, C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]),
+    ("svo_pose_graph_edge", C.c_int, [_f64p, _f64p, _f64p]),
     ("svo_bundle_adjust", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
                                     _i32p, _i32p, _f32p, _f64p, C.c_double, C.c_int, _f64p, _i32p]),
     ("svo_ba_linearize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p, _u8p, _f64p,
@@ -1286,6 +1293,89 @@ class Context:
             _p(cnt, _i32p) if cnt is not None else None, P, n, _p(K, _f64p), float(baseline), float(huber_delta),
             int(max_iterations), _p(poses, _f64p), int(reps), _p(ms[0:], _f64p), _p(ms[1:], _f64p)))
         return {"ms_device": float(ms[0]), "ms_host": float(ms[1])}
+
+    # ---------------------------------------------------------------- pose graph
+    @staticmethod
+    def _pg_args(poses, fixed, edge_ij, edge_Z, edge_info, n_nodes, n_edges):
+        """One problem (poses (N, 12), edges (E, ...)) or a batch (a leading axis P on
+        every array) -> the C ABI's arguments; (single, P, N, E, ...)."""
+        poses = np.array(poses, np.float64)
+        single = poses.ndim == 2
+        edge_ij = np.asarray(edge_ij)
+        if single:
+            poses, edge_ij = poses[None], edge_ij.reshape(1, -1, 2)
+        P, N, E = poses.shape[0], poses.shape[1], edge_ij.shape[1]
+        poses = np.ascontiguousarray(poses.reshape(P, N, 12))
+        fixed = _c(np.asarray(fixed, np.uint8).reshape(P, N), np.uint8)
+        edge_ij = _c(edge_ij.reshape(P, E, 2), np.int32)
+        edge_Z = _c(np.asarray(edge_Z).reshape(P, E, 12), np.float64)
+        edge_info = _c(np.asarray(edge_info).reshape(P, E, 21), np.float64)
+        cnt = [None if c is None else _c(np.asarray(c).reshape(P), np.int32) for c in (n_nodes, n_edges)]
+        return single, P, N, E, poses, fixed, edge_ij, edge_Z, edge_info, cnt
+
+    def pose_graph_optimize(self, poses, fixed, edge_ij, edge_Z, edge_info, n_nodes=None, n_edges=None,
+                            huber_delta: float = 0.0, max_iterations: int = 50, max_cg: int = 1024):
+        """Pose-graph optimisation, the whole LM of every problem in one launch
+        (svo_pose_graph_optimize): poses (P, N, 12) world -> camera, fixed (P, N)
+        bool, edges edge_ij (P, E, 2) int pairs (i, j), edge_Z (P, E, 12) the measured
+        T_j T_i^-1, edge_info (P, E, 21) the upper triangle of the 6x6 information
+        matrix in the order (rho, phi) -- the first 21 of refine_poses_stereo's normal;
+        n_nodes / n_edges: (P,) counts of a ragged batch. One problem may be given
+        without the leading axis. -> (poses, costs (P, 2): initial and final,
+        iterations (P,), cg_iterations (P,): matrix-vector products of the run).
+        max_iterations = 0: the first cost twice, the poses' bits kept."""
+        single, P, N, E, poses, fixed, ij, Z, info, cnt = self._pg_args(poses, fixed, edge_ij, edge_Z, edge_info,
+                                                                        n_nodes, n_edges)
+        costs = np.zeros((P, 2), np.float64)
+        its, cgs = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        out = poses.copy()
+        self._check(lib().svo_pose_graph_optimize(
+            self.handle, P, N, E, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
+            _p(fixed, _u8p), _p(ij, _i32p), _p(Z, _f64p), _p(info, _f64p), float(huber_delta), int(max_iterations),
+            int(max_cg), _p(out, _f64p), _p(costs, _f64p), _p(its, _i32p), _p(cgs, _i32p)))
+        if single:
+            return out[0], costs[0], int(its[0]), int(cgs[0])
+        return out, costs, its, cgs
+
+    def pose_graph_linearize(self, poses, fixed, edge_ij, edge_Z, edge_info, n_nodes=None, n_edges=None,
+                             huber_delta: float = 0.0) -> dict:
+        """The pose graph's first linearisation at the given poses
+        (svo_pose_graph_linearize) -> dict of cost (P,), e (P, E, 6), w (P, E), Ji and
+        Jj (P, E, 6, 6), node (P, N, 27): each node's 21 + 6 sums; without the leading
+        axis for one problem. Entries beyond a problem's counts are zero."""
+        single, P, N, E, poses, fixed, ij, Z, info, cnt = self._pg_args(poses, fixed, edge_ij, edge_Z, edge_info,
+                                                                        n_nodes, n_edges)
+        out = {"cost": np.zeros(P), "e": np.zeros((P, E, 6)), "w": np.zeros((P, E)), "Ji": np.zeros((P, E, 6, 6)),
+               "Jj": np.zeros((P, E, 6, 6)), "node": np.zeros((P, N, 27))}
+        self._check(lib().svo_pose_graph_linearize(
+            self.handle, P, N, E, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
+            _p(fixed, _u8p), _p(ij, _i32p), _p(Z, _f64p), _p(info, _f64p), float(huber_delta),
+            *[_p(out[k], _f64p) for k in ("cost", "e", "w", "Ji", "Jj", "node")]))
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def pose_graph_time(self, poses, fixed, edge_ij, edge_Z, edge_info, n_nodes=None, n_edges=None,
+                        huber_delta: float = 0.0, max_iterations: int = 50, max_cg: int = 1024, reps: int = 5) -> dict:
+        """ms per whole launch of pose_graph_optimize (HIP events, svo_pose_graph_time)
+        with the last launch's iterations and cg_iterations (P,)."""
+        single, P, N, E, poses, fixed, ij, Z, info, cnt = self._pg_args(poses, fixed, edge_ij, edge_Z, edge_info,
+                                                                        n_nodes, n_edges)
+        ms = np.zeros(1)
+        its, cgs = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        self._check(lib().svo_pose_graph_time(
+            self.handle, P, N, E, *[None if c is None else _p(c, _i32p) for c in cnt], _p(poses, _f64p),
+            _p(fixed, _u8p), _p(ij, _i32p), _p(Z, _f64p), _p(info, _f64p), float(huber_delta), int(max_iterations),
+            int(max_cg), int(reps), _p(ms, _f64p), _p(its, _i32p), _p(cgs, _i32p)))
+        return {"ms": float(ms[0]), "iterations": its, "cg_iterations": cgs}
+
+    @staticmethod
+    def pose_graph_edge(Ti, Tj) -> np.ndarray:
+        """Z = T_j T_i^-1 (12,), the measurement of an edge (i, j) that the two poses
+        agree with (svo_pose_graph_edge): the solver's own arithmetic, on the host."""
+        Ti, Tj = _c(np.asarray(Ti, np.float64).reshape(12), np.float64), _c(np.asarray(Tj, np.float64).reshape(12), np.float64)
+        Z = np.zeros(12)
+        if lib().svo_pose_graph_edge(_p(Ti, _f64p), _p(Tj, _f64p), _p(Z, _f64p)) != 0:
+            raise SvoError("svo_pose_graph_edge: bad arguments")
+        return Z
 
     # ---------------------------------------------------------------- bundle adjustment
     @staticmethod

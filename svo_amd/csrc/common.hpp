@@ -83,6 +83,7 @@ enum ScratchSlot {
                         // synchronise as they enter: upload_raw returns with its kernel in flight)
     kScratchRefine,     // refine_device.cpp's entries, svo_frontend_refine_poses
     kScratchFit,        // svo_pnp_score, svo_sqpnp_stats, svo_sqpnp_fit, svo_trig_pa
+    kScratchPoseGraph,  // pose_graph_api.cpp's entries
     kScratchSlots       // the count
 };
 }  // namespace svo
